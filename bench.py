@@ -6,6 +6,13 @@ synthetic YCSB batch: 1,048,576 txns x 16 keys, zipf theta 0.9, 16,777,216-key
 table, TXN_WRITE_PERC = TUP_WRITE_PERC = 0.5 (SURVEY.md §8(d) "Headline").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--txns N] [--theta T]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+decisions if --dump-outputs is given and prints the result line.  --full adds
+everything else the line can carry: the one-epoch-at-a-time latency, the
+per-phase kernel times, the stream-copy peak, the parity checks against the
+oracle, the CPU baselines and the other BASELINE configs.
 
 N > 1 is launched by torch.distributed.run (one rank per GPU, RCCL): keys are
 hash-sharded across the ranks and every round joins a per-txn state allreduce.
@@ -42,11 +49,19 @@ def parse():
     ap.add_argument("--theta", type=float, default=0.9)
     ap.add_argument("--keys", type=int, default=16)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0xD3E7A001)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: "
+                         "single-epoch latency, per-phase times, stream-copy peak, parity "
+                         "against the oracle, the CPU baselines and the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed in DIR/<name>.npy "
+                         "(float32 / float64): the decisions of the last epoch of every lane")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=131072,
                     help="txns of the batch timed with the CPU reference restatement")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the other BASELINE configs (C2, C3, C4, C5) at N=1")
+                    help="with --full: skip the other BASELINE configs (C2, C3, C4, C5) at N=1")
     ap.add_argument("--only", default="",
                     help="comma-separated secondary configs to run INSTEAD of the headline "
                          "(profiling aid): " + ",".join(CONFIGS))
@@ -77,7 +92,10 @@ def parse():
     ap.add_argument("--exchange", choices=["rccl", "host"], default="rccl",
                     help="N>1 status all-reduce: RCCL over xGMI (one GPU per rank), or "
                          "host/gloo (rehearsal: ranks may share one GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.only and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline's outputs; not with --only")
+    return args
 
 
 def stream_copy_gbps(dev, mib=2048, reps=10):
@@ -734,6 +752,31 @@ def snapshot_config(eng, dev, timed, orc, n=1 << 20, check=131072):
             "parity_sample": f"first {check} txns"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, rcs, stats):
+    """--dump-outputs: what the caller of the timed path holds after its last
+    step.  rc_lane<i>.npy: the decisions (0 commit, else the abort code) of the
+    last epoch of lane i, one float32 per txn (rc.npy when nothing is
+    pipelined); where they would pass the budget, the txns of a fixed seeded
+    sample (the same for every lane, indices in sample_idx.npy).  counts.npy:
+    [commits, aborts] of the last epochs' stats, submit order, float64."""
+    os.makedirs(path, exist_ok=True)
+    n = int(rcs[0].numel())
+    keep = (DUMP_BUDGET_BYTES - 4096) // (4 * len(rcs) + 8)  # 4 B per lane + the index, headers
+    idx = None
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0xD3E7A0D0).choice(n, size=keep, replace=False))
+        np.save(os.path.join(path, "sample_idx.npy"), idx.astype(np.float64))
+    for i, rc in enumerate(rcs):
+        a = rc.cpu().numpy()
+        a = (a if idx is None else a[idx]).astype(np.float32)
+        np.save(os.path.join(path, f"rc_lane{i}.npy" if len(rcs) > 1 else "rc.npy"), a)
+    np.save(os.path.join(path, "counts.npy"),
+            np.array([[s["n_commit"], s["n_abort"]] for s in stats], np.float64))
+
+
 def main():
     args = parse()
     import torch
@@ -859,12 +902,90 @@ def main():
             dt, pipe_stats = timed_region(lambda: run_pipelined(args.steps))
         finally:
             gc.enable()
-    # one epoch at a time: the single-epoch latency (device events per epoch)
-    for _ in range(args.warmup):
-        step()
-    dt_lat, stats = timed_region(lambda: [step() for _ in range(args.steps)])
+    # one epoch at a time: the timed path where nothing is pipelined (N > 1,
+    # --pipeline 0); beside a pipelined headline it is the single-epoch
+    # latency (device events per epoch), measured under --full only
+    dt_lat, stats = None, None
+    if dt is None or args.full:
+        for _ in range(args.warmup):
+            step()
+        dt_lat, stats = timed_region(lambda: [step() for _ in range(args.steps)])
     if dt is None:
         dt = dt_lat
+    ms_per_step = dt / args.steps * 1e3
+    value = n_total * args.steps / dt
+    # the headline's roofline: algorithmic bytes of the epochs over the timed
+    # region (throughput basis; wall clock, so host gaps count against it)
+    timed_stats = pipe_stats or stats
+    alg_per_epoch = float(np.mean([s["alg_bytes"] for s in timed_stats]))
+    if pipe_stats:
+        epoch_gbs, basis_ms = alg_per_epoch * args.steps / dt / 1e9, ms_per_step
+    else:
+        basis_ms = float(np.mean([s["device_ms"] for s in stats]))
+        epoch_gbs = stats[-1]["alg_bytes"] / (basis_ms * 1e-3) / 1e9
+
+    if args.dump_outputs and rank == 0:
+        last = timed_stats[-lanes:] if lanes else timed_stats[-1:]
+        dump_outputs(args.dump_outputs, pipe_outs if lanes else [out_rc], last)
+
+    line = {
+        "metric": "OCC-validated txns/sec, YCSB theta=0.9",
+        "value": value,
+        "unit": "txns/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (deterministic YCSB generator, restated gen_requests_zipf)",
+        "config": {
+            "workload": f"YCSB OCC epoch validation, {n_total} txns x {args.keys} keys, "
+                        f"zipf theta={args.theta}, 16,777,216-key table, 50% RO txns, "
+                        f"50% WR tuples",
+            "global_batch": n_total,
+            "keys_per_txn": args.keys,
+            "parallelism": (f"key-shard x{world} ({args.exchange} kill-bit all-gather, whole epoch per rank)" if world > 1
+                            else "single GPU"),
+        },
+        "pipeline": ({
+            "lanes": lanes,
+            "partition": ("lane i on 1/lanes of every XCD's CUs (CU-masked streams)"
+                          if args.partition else "every lane on the whole chip"),
+            "ms_per_epoch_steady": ms_per_step,
+            "txns_per_s": value,
+            "batches": f"{lanes} distinct resident batches (seeds {args.seed:#x}+0..{lanes - 1}), "
+                       f"epoch k on lane k mod {lanes}",
+            "parity_vs_oracle_per_lane": None,
+            "epoch_span_ms_mean": float(np.mean([s["device_ms"] for s in pipe_stats])),
+            "host_us_per_epoch": {"submit": host_split[0] / args.steps * 1e6,
+                                  "wait": host_split[1] / args.steps * 1e6},
+        } if pipe_stats else None),
+        "roofline": {
+            "bound": "hbm",
+            "scope": ("whole epochs, throughput basis: algorithmic bytes of the K pipelined "
+                      "epochs over the timed region's wall clock (SURVEY.md 8(d)); "
+                      "single-epoch latency basis in single_epoch" if pipe_stats else
+                      "whole epoch: every kernel of dcc_occ_validate_epoch, HIP events "
+                      "around the epoch on the engine stream (SURVEY.md 8(d))"),
+            "achieved": epoch_gbs,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": epoch_gbs / HBM_PEAK_GBS,
+            "alg_bytes_per_launch": int(alg_per_epoch),
+            "avg_launch_ms": basis_ms,
+        },
+        "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # per-phase kernel times (HIP events on the engine stream), separate pass
     eng.set_profiling(True)
@@ -883,18 +1004,10 @@ def main():
 
     copies = stream_copy_both(f"cuda:{local}") if rank == 0 else None
     copy_gbps = max(v for v in copies.values() if v) if copies else None
+    # the single-epoch latency basis, kept beside the headline's roofline
     s0 = stats[-1]
-    ms_per_step = dt / args.steps * 1e3
-    value = n_total * args.steps / dt
     dev_ms = float(np.mean([s["device_ms"] for s in stats]))
     lat_gbs = s0["alg_bytes"] / (dev_ms * 1e-3) / 1e9
-    # the headline's roofline: algorithmic bytes of the epochs over the timed
-    # region (throughput basis; wall clock, so host gaps count against it);
-    # the single-epoch latency basis is kept beside it
-    alg_per_epoch = (float(np.mean([s["alg_bytes"] for s in pipe_stats])) if pipe_stats
-                     else float(s0["alg_bytes"]))
-    epoch_gbs = alg_per_epoch * args.steps / dt / 1e9 if pipe_stats else lat_gbs
-    basis_ms = dt / args.steps * 1e3 if pipe_stats else dev_ms  # time per epoch of the roofline
 
     # parity check of the measured decisions against the oracle (rank 0, N=1)
     parity = None
@@ -949,41 +1062,9 @@ def main():
                     "top_kernels": {k: {"fetch_bytes": v.get("fetch_bytes", v.get("fetch_bytes_max")),
                                         "write_bytes": v.get("write_bytes", v.get("write_bytes_max")),
                                         "l2_hit": v.get("l2_hit")} for k, v in top}}
-        line = {
-            "metric": "OCC-validated txns/sec, YCSB theta=0.9",
-            "value": value,
-            "unit": "txns/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong" if args.strong else "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic (deterministic YCSB generator, restated gen_requests_zipf)",
-            "config": {
-                "workload": f"YCSB OCC epoch validation, {n_total} txns x {args.keys} keys, "
-                            f"zipf theta={args.theta}, 16,777,216-key table, 50% RO txns, "
-                            f"50% WR tuples",
-                "global_batch": n_total,
-                "keys_per_txn": args.keys,
-                "parallelism": (f"key-shard x{world} ({args.exchange} kill-bit all-gather, whole epoch per rank)" if world > 1
-                                else "single GPU"),
-            },
-            "pipeline": ({
-                "lanes": lanes,
-                "partition": ("lane i on 1/lanes of every XCD's CUs (CU-masked streams)"
-                              if args.partition else "every lane on the whole chip"),
-                "ms_per_epoch_steady": dt / args.steps * 1e3,
-                "txns_per_s": value,
-                "batches": f"{lanes} distinct resident batches (seeds {args.seed:#x}+0..{lanes - 1}), "
-                           f"epoch k on lane k mod {lanes}",
-                "parity_vs_oracle_per_lane": pipe_parity,
-                "epoch_span_ms_mean": float(np.mean([s["device_ms"] for s in pipe_stats])),
-                "host_us_per_epoch": {"submit": host_split[0] / args.steps * 1e6,
-                                      "wait": host_split[1] / args.steps * 1e6},
-            } if pipe_stats else None),
+        if line["pipeline"]:
+            line["pipeline"]["parity_vs_oracle_per_lane"] = pipe_parity
+        line.update({
             "single_epoch": {
                 "ms_per_epoch_wall": dt_lat / args.steps * 1e3,
                 "txns_per_s": n_total * args.steps / dt_lat,
@@ -992,16 +1073,7 @@ def main():
                 "hbm_frac": lat_gbs / HBM_PEAK_GBS,
             },
             "roofline": {
-                "bound": "hbm",
-                "scope": ("whole epochs, throughput basis: algorithmic bytes of the K pipelined "
-                          "epochs over the timed region's wall clock (SURVEY.md 8(d)); "
-                          "single-epoch latency basis in single_epoch" if pipe_stats else
-                          "whole epoch: every kernel of dcc_occ_validate_epoch, HIP events "
-                          "around the epoch on the engine stream (SURVEY.md 8(d))"),
-                "achieved": epoch_gbs,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": epoch_gbs / HBM_PEAK_GBS,
+                **line["roofline"],
                 "stream_copy_GBps": copy_gbps,
                 "stream_copy_variants_GBps": copies,
                 "frac_of_stream_copy": epoch_gbs / copy_gbps if copy_gbps else None,
@@ -1013,8 +1085,6 @@ def main():
                            "filter": _kern_l2(hp, "k_sw_filter"),
                            "serial_pass": _kern_l2(hp, "k_sw_seq"),
                            "pre_pass": _kern_l2(hp, "k_sw_pre")} if hp else None,
-                "alg_bytes_per_launch": int(alg_per_epoch),
-                "avg_launch_ms": basis_ms,
                 "streaming_kernel": filt,
             },
             "epoch": {
@@ -1035,7 +1105,7 @@ def main():
             },
             "cpu_baseline": cpu,
             "other_configs": secondary,
-        }
+        })
         print(json.dumps(line), flush=True)
     eng.close()
     if world > 1:

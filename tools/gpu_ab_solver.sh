@@ -8,7 +8,7 @@ mkdir -p "$O"
 cd "$R"
 for v in ${VARIANTS:-3:0 4:1 4:2 4:3}; do
   s=${v%%:*}; l=${v##*:}
-  timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --solver $s --ck-level $l > "$O/h_$s_$l.json" 2> "$O/h.err" || { tail -5 "$O/h.err"; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --solver $s --ck-level $l > "$O/h_$s_$l.json" 2> "$O/h.err" || { tail -5 "$O/h.err"; exit 1; }
   timeout -k 10 300 python -u bench.py --only C2,C3,C5 --steps 10 --warmup 3 --solver $s --ck-level $l > "$O/s_$s_$l.json" 2> "$O/s.err" || { tail -5 "$O/s.err"; exit 1; }
   python3 - "$O/h_$s_$l.json" "$O/s_$s_$l.json" "$v" <<'PY'
 import json, sys

@@ -12,11 +12,11 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout
 tail -1 "$O/gpu_suite.log"
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
 tail -3 "$O/smoke.log"
-timeout -k 10 600 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 tail -c 600 "$O/bench.json"; echo
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run \
-   -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > "$O/prof.log" 2>&1 || exit 1
+   -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > "$O/prof.log" 2>&1 || exit 1
 f=$(find "$O/prof" -name '*kernel_trace.csv' | head -1)
 python3 "$R/tools/trace_epoch.py" "$f" 3 > "$O/trace.txt"
 tail -3 "$O/trace.txt"

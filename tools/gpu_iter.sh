@@ -13,7 +13,7 @@ if [ -n "$TESTS" ]; then
      > "$O/tests.log" 2>&1 || { tail -40 "$O/tests.log"; exit 1; }
   tail -2 "$O/tests.log"
 fi
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-secondary --no-cpu-baseline ${BENCH_EXTRA} \
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-secondary --no-cpu-baseline ${BENCH_EXTRA} \
    > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
 python3 -c "
 import json
@@ -31,7 +31,7 @@ for k,v in j.items(): print(k, 'device', round(v.get('device_ms', v.get('device_
 fi
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/tr" -o run \
-   -- python3 "$R/bench.py" --steps 6 --warmup 1 --no-cpu-baseline --no-secondary ${BENCH_EXTRA} \
+   -- python3 "$R/bench.py" --full --steps 6 --warmup 1 --no-cpu-baseline --no-secondary ${BENCH_EXTRA} \
    > "$O/tr.log" 2>&1 || { tail -5 "$O/tr.log"; exit 1; }
 f=$(find "$O/tr" -name '*kernel_trace.csv' | head -1)
 python3 "$R/tools/trace_epoch.py" "$f" 2 > "$O/trace.txt"

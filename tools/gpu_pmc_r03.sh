@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT="$R/gpurun_out/${TAG:-pmc3}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-H="$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
+H="$R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
 C="$R/bench.py --only C4 --steps 2 --warmup 1"
 run() {  # name counters args...
   local n=$1 c=$2; shift 2

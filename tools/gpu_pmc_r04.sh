@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT="$R/gpurun_out/${TAG:-pmc4}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-H="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+H="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
 C="$R/bench.py --only C4 --steps 2 --warmup 1"
 S="$R/bench.py --only C2,C3,C5,MAAT_1M --steps 2 --warmup 1"
 run() {  # name counters args...

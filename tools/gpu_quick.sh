@@ -10,7 +10,7 @@ timeout -k 10 400 python -u -m pytest ${TESTS:-tests/test_gpu_sweep.py tests/tes
    --timeout 120 --timeout-method thread -m gpu > gpurun_out/q/tests.log 2>&1 \
    || { tail -40 gpurun_out/q/tests.log; exit 1; }
 tail -2 gpurun_out/q/tests.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-secondary --no-cpu-baseline ${BENCH_EXTRA} \
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-secondary --no-cpu-baseline ${BENCH_EXTRA} \
    > gpurun_out/q/bench.log 2>&1 || { tail -20 gpurun_out/q/bench.log; exit 1; }
 python3 -c "
 import json
@@ -19,7 +19,7 @@ print('ms/step', round(j['ms_per_step'],4), 'device', round(e['device_ms'],4), [
 "
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/q/tr" -o run \
-   -- python3 "$R/bench.py" --steps 4 --warmup 1 --no-cpu-baseline --no-secondary ${BENCH_EXTRA} \
+   -- python3 "$R/bench.py" --full --steps 4 --warmup 1 --no-cpu-baseline --no-secondary ${BENCH_EXTRA} \
    > "$R/gpurun_out/q/tr.log" 2>&1 || { tail -5 "$R/gpurun_out/q/tr.log"; exit 1; }
 f=$(find "$R/gpurun_out/q/tr" -name '*kernel_trace.csv' | head -1)
 python3 "$R/tools/trace_epoch.py" "$f"

@@ -4,7 +4,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-r5b}
 mkdir -p "$O"
-timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -30 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -30 "$O/bench.err"; exit 1; }
 python3 - "$O/bench.json" <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))

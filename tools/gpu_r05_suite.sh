@@ -8,7 +8,7 @@ timeout -k 10 500 python -u -m pytest -x -q --timeout 120 --timeout-method threa
 tail -2 "$O/gpu_suite.log"
 timeout -k 10 500 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
 if [ -z "$NOBENCH" ]; then
-timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 python3 - "$O/bench.json" <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))

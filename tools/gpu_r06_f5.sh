@@ -7,7 +7,7 @@ O=gpurun_out/f5
 mkdir -p $O
 one() {  # tag lib [env]
   local tag=$1 lib=$2; shift 2
-  env DENEVA_AMD_LIB=$PWD/deneva_amd/$lib "$@" timeout -k 10 150 python -u bench.py --no-secondary --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err || return 1
+  env DENEVA_AMD_LIB=$PWD/deneva_amd/$lib "$@" timeout -k 10 150 python -u bench.py --full --no-secondary --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err || return 1
   python -c "import json;d=json.load(open('$O/$tag.json'));print('$tag', round(d['ms_per_step'],4), round(d['single_epoch']['device_ms'],4), round(d['roofline']['streaming_kernel']['avg_launch_ms']*1e3,1), flush=True)"
 }
 for rep in 1 2 3; do

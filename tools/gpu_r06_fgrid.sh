@@ -6,7 +6,7 @@ O=gpurun_out/fgrid
 mkdir -p $O
 export DENEVA_AMD_LIB=$PWD/deneva_amd/libdcc_exp.so
 for fg in 1024 512 768 1536 1024; do
-  DCC_SW_FGRID=$fg timeout -k 10 150 python -u bench.py --no-secondary --no-cpu-baseline --steps 100 --warmup 10 > $O/fg_$fg.json 2> $O/fg_$fg.err || exit 1
+  DCC_SW_FGRID=$fg timeout -k 10 150 python -u bench.py --full --no-secondary --no-cpu-baseline --steps 100 --warmup 10 > $O/fg_$fg.json 2> $O/fg_$fg.err || exit 1
   python - $O/fg_$fg.json $fg <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

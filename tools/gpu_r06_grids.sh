@@ -7,7 +7,7 @@ O=gpurun_out/grids
 mkdir -p $O
 one() {  # tag lib [env...]
   local tag=$1 lib=$2; shift 2
-  env DENEVA_AMD_LIB=$PWD/deneva_amd/$lib "$@" timeout -k 10 150 python -u bench.py --no-secondary --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err || return 1
+  env DENEVA_AMD_LIB=$PWD/deneva_amd/$lib "$@" timeout -k 10 150 python -u bench.py --full --no-secondary --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err || return 1
   python - $O/$tag.json $tag <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

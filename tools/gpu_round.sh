@@ -14,7 +14,7 @@ tail -1 "$O/gpu_suite.log"
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
 tail -3 "$O/smoke.log"
 fi
-T0=$(date +%s.%N); timeout -k 10 600 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+T0=$(date +%s.%N); timeout -k 10 600 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 echo "bench wall s: $(python3 -c "print(round($(date +%s.%N) - $T0, 1))")"
 python3 -c "
 import json;j=json.load(open('$O/bench.json'));e=j['epoch'];r=j['roofline']
@@ -24,7 +24,7 @@ for k,v in j['other_configs'].items(): print(k,round(v.get('device_ms',v.get('de
 "
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run \
-   -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > "$O/prof.log" 2>&1 || exit 1
+   -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > "$O/prof.log" 2>&1 || exit 1
 f=$(find "$O/prof" -name '*kernel_trace.csv' | head -1)
 python3 "$R/tools/trace_epoch.py" "$f" 3 > "$O/trace.txt"
 tail -3 "$O/trace.txt"

@@ -9,7 +9,7 @@ i=0
 while read -r pmax lv ro; do
   [ -z "$pmax" ] && continue
   i=$((i+1))
-  DCC_SW_PMAX=$pmax timeout -k 10 200 python bench.py --steps 30 --warmup 3 --no-secondary --no-cpu-baseline \
+  DCC_SW_PMAX=$pmax timeout -k 10 200 python bench.py --full --steps 30 --warmup 3 --no-secondary --no-cpu-baseline \
      --sweep-levels $lv --ro-split $ro > "$O/s$i.json" 2>&1 || { tail -5 "$O/s$i.json"; exit 1; }
   python3 -c "
 import json

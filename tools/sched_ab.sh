@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O="$R/gpurun_out/${TAG:-sched}"; mkdir -p "$O"; cd "$R"
 for s in ${SCHEDS:-"1024,3072,8192" "1024,4096,8192" "1024,2048,8192" "2048,4096,8192" "768,3072,8192" "1024,3072,8192"}; do
-  DCC_SW_PMAX=$s timeout -k 10 120 python bench.py --steps 30 --warmup 5 --no-secondary --no-cpu-baseline \
+  DCC_SW_PMAX=$s timeout -k 10 120 python bench.py --full --steps 30 --warmup 5 --no-secondary --no-cpu-baseline \
     > "$O/b_$s.json" 2> "$O/b_$s.err" || { tail -5 "$O/b_$s.err"; exit 1; }
   python3 -c "
 import json;j=json.loads(open('$O/b_$s.json').read().strip().splitlines()[-1]);e=j['epoch']
