@@ -147,14 +147,12 @@ __global__ __launch_bounds__(256) void k_cv_prep(const uint64_t* __restrict__ ke
       // origin, FIFO): the stable rank is the identity and needs no sort
       uns += (t + 1 < n && o > order[t + 1]) ? 1u : 0u;
     }
-  for (int d = 32; d > 0; d >>= 1) {
-    kor |= __shfl_xor(kor, d);
-    kand &= __shfl_xor(kand, d);
-    oor |= __shfl_xor(oor, d);
-    oand &= __shfl_xor(oand, d);
-    nex += __shfl_xor(nex, d);
-    uns += __shfl_xor(uns, d);
-  }
+  kor = wave_reduce<OrOp<uint64_t>>(kor);
+  kand = wave_reduce<AndOp<uint64_t>>(kand);
+  oor = wave_reduce<OrOp<uint64_t>>(oor);
+  oand = wave_reduce<AndOp<uint64_t>>(oand);
+  nex = wave_reduce<AddOp<uint32_t>>(nex);
+  uns = wave_reduce<AddOp<uint32_t>>(uns);
   __shared__ uint32_t s_un[4];
   const uint32_t wv = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
@@ -208,10 +206,8 @@ __global__ __launch_bounds__(256) void k_cv_len_tiles(const uint32_t* __restrict
       s += l;
     }
   }
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) tsum[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  s = block_reduce<4, AddOp<uint32_t>>(s, sh);
+  if (threadIdx.x == 0) tsum[blockIdx.x] = s;
 }
 
 // exclusive scan of len (tile prefix from the scanned tsum) -> off2 [n+1]
@@ -225,16 +221,8 @@ __global__ __launch_bounds__(256) void k_cv_len_apply(const uint32_t* __restrict
     v[i] = base + i < n ? len[base + i] : 0u;
     s += v[i];
   }
-  const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
-  uint32_t x = s;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) sh[wv] = x;
-  __syncthreads();
-  uint32_t run = tpre[blockIdx.x] + x - s;
-  for (uint32_t w = 0; w < wv; w++) run += sh[w];
+  uint32_t tot;
+  uint32_t run = tpre[blockIdx.x] + block_excl<4, AddOp<uint32_t>>(s, sh, tot);
   for (uint32_t i = 0; i < CV_ITEMS; i++) {
     if (base + i < n) off2[base + i] = run;
     run += v[i];
@@ -268,15 +256,10 @@ __global__ __launch_bounds__(256) void k_cv_layout(const uint32_t* __restrict__ 
     src = off[t];
     len = off[t + 1] - src;
   }
-  uint32_t x = len;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  const uint32_t total = __shfl(x, 63);
+  uint32_t total;
+  const uint32_t pre = wave_excl<AddOp<uint32_t>>(len, total);
   s_src[w][lane] = src;
-  s_pre[w][lane] = x - len;
+  s_pre[w][lane] = pre;
   s_t[w][lane] = t;
   if (lane == 0) s_pre[w][64] = total;
   __builtin_amdgcn_wave_barrier();
@@ -602,7 +585,8 @@ __global__ __launch_bounds__(256) void k_cv_up_l(const K* __restrict__ sk,
     }
   }
   uint32_t total;
-  (void)gl_block_excl(acc, s_w, total);
+  (void)block_excl<GlOp>(acc, s_w, blockDim.x >> 6, total);
+  __syncthreads();
   if (threadIdx.x == 0) agg[blockIdx.x] = total;
   if (hcnt) {  // the tile's counts of the write-out partition digit (txn's top bits)
     s_h[threadIdx.x] = 0;
@@ -628,7 +612,8 @@ __global__ __launch_bounds__(256) void k_cv_top_l(uint32_t* __restrict__ agg, ui
       v = gl_combine(v, a[q]);
     }
     uint32_t total;
-    uint32_t run = gl_combine(carry, gl_block_excl(v, s_w, total));
+    uint32_t run = gl_combine(carry, block_excl<GlOp>(v, s_w, blockDim.x >> 6, total));
+    __syncthreads();  // s_w free for the next step
 #pragma unroll
     for (uint32_t q = 0; q < 16; q++) {
       if (i0 + q < tiles) agg[i0 + q] = run;
@@ -678,7 +663,8 @@ __global__ __launch_bounds__(256) void k_cv_down_l(const K* __restrict__ sk,
     }
   }
   uint32_t total;
-  uint32_t run = gl_combine(pre[blockIdx.x], gl_block_excl(acc, s_w, total));
+  uint32_t run = gl_combine(pre[blockIdx.x], block_excl<GlOp>(acc, s_w, blockDim.x >> 6, total));
+  __syncthreads();
   if (po.ko) {
     // (1) per digit: the tile's count (LDS), its tile-local base (scan over
     // digits) and its global base (digit totals before it + this tile's
@@ -706,30 +692,15 @@ __global__ __launch_bounds__(256) void k_cv_down_l(const K* __restrict__ sk,
     }
     __syncthreads();
     {
-      const uint32_t c = s_run[tid], t = po.tot[tid];
-      uint32_t x = c, y = t;  // inclusive wave scans of the tile counts and the totals
-#pragma unroll
-      for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t xu = __shfl_up(x, d), yu = __shfl_up(y, d);
-        if ((tid & 63u) >= d) {
-          x += xu;
-          y += yu;
-        }
-      }
-      __shared__ uint32_t s_wx[4], s_wy[4];
-      if ((tid & 63u) == 63u) {
-        s_wx[tid >> 6] = x;
-        s_wy[tid >> 6] = y;
-      }
-      __syncthreads();
-      uint32_t bx = 0, by = 0;
-      for (uint32_t w = 0; w < (tid >> 6); w++) {
-        bx += s_wx[w];
-        by += s_wy[w];
-      }
-      s_tb[tid] = bx + x - c;
-      s_gb[tid] = by + y - t + po.hcnt[(uint64_t)tid * gridDim.x + blockIdx.x];
-      s_run[tid] = bx + x - c;
+      // exclusive scans over the 256 digits of the tile counts (low word) and
+      // the totals (high word) in one: neither sum reaches 2^32
+      __shared__ uint64_t s_wxy[4];
+      uint64_t tt;
+      const uint64_t e = block_excl<4, AddOp<uint64_t>>((uint64_t)s_run[tid] | ((uint64_t)po.tot[tid] << 32),
+                                                        s_wxy, tt);
+      s_tb[tid] = (uint32_t)e;
+      s_gb[tid] = (uint32_t)(e >> 32) + po.hcnt[(uint64_t)tid * gridDim.x + blockIdx.x];
+      s_run[tid] = (uint32_t)e;
     }
     __syncthreads();
     // (2) the tile's pairs in digit order through LDS (any order within a digit)
@@ -909,7 +880,7 @@ __global__ __launch_bounds__(256) void k_cv_wave(WaveArgs a) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       if (pg != NOPOS)
         lvl = __hip_atomic_load(&a.maxl[pg], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-      for (int d = 32; d > 0; d >>= 1) lvl = max(lvl, (uint32_t)__shfl_xor(lvl, d));
+      lvl = wave_reduce<MaxOp<uint32_t>>(lvl);
     }
     if (g != NOPOS) __hip_atomic_fetch_max(&a.maxl[g], lvl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -933,10 +904,8 @@ __global__ __launch_bounds__(256) void k_cv_count(const uint8_t* __restrict__ rc
     r += rc[t] == DCC_RC_RCOK;
     if (wave) mw = max(mw, wave[t]);
   }
-  for (int d = 32; d > 0; d >>= 1) {
-    r += __shfl_xor(r, d);
-    mw = max(mw, (uint32_t)__shfl_xor(mw, d));
-  }
+  r = wave_reduce<AddOp<uint32_t>>(r);
+  mw = wave_reduce<MaxOp<uint32_t>>(mw);
   if ((threadIdx.x & 63) == 0) {
     s[0][threadIdx.x >> 6] = r;
     s[1][threadIdx.x >> 6] = mw;

@@ -112,31 +112,11 @@ __device__ inline uint32_t cb_hput(uint32_t* t, uint32_t r, uint32_t v, uint32_t
 
 __device__ inline uint32_t stg_ix(uint32_t p) { return p + (p >> 5); }
 
-// LDS-only workgroup barrier: waits for this wave's LDS operations, not for
-// its outstanding global loads, stores or returning atomics.
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Exclusive add-scan of one u32 per thread over the workgroup (LDS barriers
-// only); s_w holds one word per wave.
+// Exclusive add-scan of one u32 per thread over the workgroup, with LDS
+// barriers only (the outstanding global loads, stores and returning atomics
+// stay in flight); s_w holds one word per wave and is reused by every call.
 __device__ inline uint32_t blk_excl_add(uint32_t v, uint32_t* s_w, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  lds_barrier();  // s_w free (an earlier call's readers are done)
-  if (lane == 63) s_w[w] = x;
-  lds_barrier();
-  uint32_t off = 0;
-  total = 0;
-  for (uint32_t q = 0; q < nw; q++) {
-    const uint32_t s = s_w[q];
-    if (q < w) off += s;
-    total += s;
-  }
-  return off + x - v;
+  return block_excl_reuse<AddOp<uint32_t>, SyncLds>(v, s_w, blockDim.x >> 6, total);
 }
 
 // Lanes of the wave whose nbits-bit bucket equals this lane's (NB > 0: a
@@ -216,16 +196,11 @@ __device__ inline uint32_t cb_wave_elems(const CbSrc& s, uint32_t q0, uint32_t n
         s_t[i] = t;
         s_b[i] = b;  // (the count pass passes s_b == s_t: only b is read there)
       }
-      uint32_t x = len;  // inclusive wave scan of the lengths
-#pragma unroll
-      for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-      }
-      const uint32_t p = run + x - len;
+      uint32_t tot;
+      const uint32_t p = run + wave_excl<AddOp<uint32_t>>(len, tot);
       // (the plan keeps wt * maxlen <= 1024; the clamp only guards the LDS)
       for (uint32_t r = 0; r < len && p + r < 1024u; r++) s_m[p + r] = (uint16_t)((i << 6) | r);
-      run += __shfl(x, 63);
+      run += tot;
     }
     ne = min(run, 1024u);
   }
@@ -470,29 +445,6 @@ __device__ inline void cb_mask_chunk(uint32_t nc, uint32_t p0, uint64_t (&e)[CB_
   for (uint32_t i = 0; i < CB_IT; i++) e[i] = p0 + i < nc ? e[i] : ~0ull;
 }
 
-// calvin_gl.h's block scan with LDS-only barriers (the outstanding
-// reservations and next-chunk loads stay in flight)
-__device__ inline uint32_t gl_block_excl_lds(uint32_t v, uint32_t* s_w, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= d) x = gl_combine(y, x);
-  }
-  lds_barrier();  // s_w free
-  if (lane == 63) s_w[w] = x;
-  lds_barrier();
-  uint32_t wp = GL_ID;
-  total = GL_ID;
-  for (uint32_t q = 0; q < nw; q++) {
-    if (q < w) wp = gl_combine(wp, s_w[q]);
-    total = gl_combine(total, s_w[q]);
-  }
-  const uint32_t ex_in = __shfl_up(x, 1);
-  return gl_combine(wp, lane ? ex_in : GL_ID);
-}
-
 template <bool H>  // the hashed carry table (row bits > CB_LB_MAX)
 __global__ __launch_bounds__(CB_BT) void k_cb_bucket(CbBucket a) {
   __shared__ uint32_t s_tab[1u << CB_LB_MAX];
@@ -708,7 +660,7 @@ __global__ __launch_bounds__(CB_BT) void k_cb_bucket(CbBucket a) {
       }
       uint32_t total;
       const uint32_t run =  // every table read is done past this
-          gl_block_excl_lds(gl_pack(lflag, lft, llt, lcnt), s_w, total);
+          block_excl_reuse<GlOp, SyncLds>(gl_pack(lflag, lft, llt, lcnt), s_w, blockDim.x >> 6, total);
       // a "same txn" flag lives one chunk: the rows flagged by the previous
       // chunk lose it before this chunk's row states go in
       {

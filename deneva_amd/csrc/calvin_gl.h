@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dcc_device.h"
+#include "dcc_scan.h"
 
 namespace dcc {
 
@@ -32,28 +32,14 @@ __device__ inline uint32_t gl_combine(uint32_t A, uint32_t B) {
   return (A & 1u) | (ft << 1) | (lt << 3) | (((A >> 5) + (B >> 5) + (bnd ? 1u : 0u)) << 5);
 }
 
-// Inclusive scan of a wave, then the block's exclusive prefix of each thread
-// (blockDim.x / 64 waves, at most 16; the wave totals through LDS s_w); returns
-// the exclusive prefix and the block total.
-__device__ inline uint32_t gl_block_excl(uint32_t v, uint32_t* s_w, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= d) x = gl_combine(y, x);
-  }
-  if (lane == 63) s_w[w] = x;
-  __syncthreads();
-  uint32_t wp = GL_ID;
-  total = GL_ID;
-  for (uint32_t q = 0; q < nw; q++) {
-    if (q < w) wp = gl_combine(wp, s_w[q]);
-    total = gl_combine(total, s_w[q]);
-  }
-  const uint32_t ex_in = __shfl_up(x, 1);
-  __syncthreads();
-  return gl_combine(wp, lane ? ex_in : GL_ID);
-}
+// the state as a scan operator (dcc_scan.h); not commutative, so it has no
+// shfl_xor and the butterfly reductions do not take it
+struct GlOp {
+  using T = uint32_t;
+  static constexpr bool has_inverse = false;
+  __device__ static uint32_t identity() { return GL_ID; }
+  __device__ static uint32_t combine(uint32_t a, uint32_t b) { return gl_combine(a, b); }
+  __device__ static uint32_t shfl_up(uint32_t v, uint32_t d) { return __shfl_up(v, d); }
+};
 
 }  // namespace dcc

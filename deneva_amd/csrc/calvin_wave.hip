@@ -54,21 +54,11 @@ __device__ inline void cw_st_l2(__amdgpu_buffer_rsrc_t r, uint32_t idx, uint32_t
   __builtin_amdgcn_raw_buffer_store_b32(v, r, idx * 4u, 0, 16);
 }
 
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // Hand-offs between the walker's workgroup and the helper workgroups (other
-// CUs, any XCD): every handed-off word is stored and loaded with agent-scope
-// relaxed atomics (global_store / global_load sc1: past the L1, write-through)
-// or changed by agent-scope atomics; a storing wave waits for its stores
-// (vmcnt 0) before the flag that covers them is raised (MI355X_MICROARCH.md,
-// inter-workgroup visibility, the sc1 hand-off row).
-__device__ inline uint32_t ag_ld(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline void ag_st(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// CUs, any XCD) are the sc1 hand-off of dcc_device.h: every handed-off word
+// is stored and loaded with dev_st / dev_ld or changed by agent-scope atomics;
+// a storing wave waits for its stores (vm_drain) before the flag that covers
+// them is raised.
 // help block: [0] chunks published by the walker's workgroup, [16] helper
 // iterations done (summed over helpers), [32] abort (a poll gave up), then the
 // bounds of every chunk's txns and the waves of every chunk, in sequence order
@@ -76,8 +66,8 @@ constexpr uint32_t CW_HP = 0, CW_HR = 16, CW_HAB = 32, CW_HDATA = 64;
 constexpr uint32_t CW_POLL_MAX = 1u << 22;  // ~0.2 s of s_sleep(2) per poll
 // wait until *ctr >= target; false when this or another poll gave up
 __device__ inline bool cw_poll(uint32_t* help, uint32_t at, uint32_t target) {
-  for (uint32_t k = 0; ag_ld(help + at) < target; k++) {
-    if (ag_ld(help + CW_HAB)) return false;
+  for (uint32_t k = 0; dev_ld(help + at) < target; k++) {
+    if (dev_ld(help + CW_HAB)) return false;
     if (k >= CW_POLL_MAX) {
       __hip_atomic_fetch_or(help + CW_HAB, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return false;
@@ -329,12 +319,12 @@ __global__ __launch_bounds__(CW_T) void k_cw_walk(CwPlan p, CwArgs a) {
         }
         // chunk c-1's member of a group ending three or more chunks ahead
         if ((w1 >> 16) == F_FAR && (x1 >> 16) == F_NONE)
-          __hip_atomic_fetch_max(a.mg + o1, ag_ld(wsq + (uint64_t)cp * C + (l >> lg)) + 1u,
+          __hip_atomic_fetch_max(a.mg + o1, dev_ld(wsq + (uint64_t)cp * C + (l >> lg)) + 1u,
                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // chunk c+2's request after a group that ended three or more chunks back
-        uint32_t v = ((w2 & F_NONE) == F_FAR && (x2 & F_NONE) == F_NONE) ? ag_ld(a.mg + p2) : 0u;
+        uint32_t v = ((w2 & F_NONE) == F_FAR && (x2 & F_NONE) == F_NONE) ? dev_ld(a.mg + p2) : 0u;
         for (uint32_t d = 1; d < L; d <<= 1) v = max(v, (uint32_t)__shfl_xor(v, d));
-        if ((l & (L - 1u)) == 0) ag_st(sEg + (uint64_t)c2 * C + (l >> lg), v);
+        if ((l & (L - 1u)) == 0) dev_st(sEg + (uint64_t)c2 * C + (l >> lg), v);
       }
       if (hid * CW_T >= H) {  // no slots this iteration: only the wait
         if (wid == 0 && !cw_poll(a.help, CW_HP, c)) spun = true;
@@ -568,7 +558,7 @@ __global__ __launch_bounds__(CW_T) void k_cw_walk(CwPlan p, CwArgs a) {
         // the staging wave whose count completes this iteration's raises P
         // (a counter of its own: a wave may reach the sync in (B) before
         // another has counted here)
-        if (lane == 0 && atomicAdd(&s_pub, 1u) == CW_HWAVES * c - 1u) ag_st(a.help + CW_HP, c);
+        if (lane == 0 && atomicAdd(&s_pub, 1u) == CW_HWAVES * c - 1u) dev_st(a.help + CW_HP, c);
         // the outputs (not handed off)
         for (uint32_t ql = h; ql < nqp; ql += CW_HELP) {
           const uint32_t q = cp * C + ql;

@@ -183,6 +183,40 @@ struct LdsMin {
 
 __device__ inline uint64_t ballot64(bool p) { return __ballot(p); }
 __device__ inline uint32_t lane_id() { return __lane_id(); }
+// the lanes below this one
+__device__ inline uint64_t lanemask_lt() {
+  const uint32_t l = lane_id();
+  return l ? (~0ull >> (64 - l)) : 0ull;
+}
+
+// Workgroup barrier that waits for the wave's LDS operations only
+// (__syncthreads() also drains its global loads and stores).
+__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The sc1 hand-off between workgroups (other CUs, any XCD; look-back scans,
+// the Calvin walker's helpers).  A handed-off word is stored and loaded with
+// agent-scope relaxed atomics: global_store / global_load sc1, write-through
+// past the L1 and read at the coherence point, so it is coherent across the
+// XCDs' L2s without a cache write-back.  The word that announces a payload is
+// the flag of a message-passing pair ordered by the hardware, not by the HIP
+// memory model's release/acquire: the writer stores the payload with dev_st,
+// waits with vm_drain() until every one of those stores is acknowledged at
+// the coherence point, then stores the flag; a reader issues its payload
+// loads (dev_ld) only after its flag load has returned the expected value
+// (its branch depends on it).  The model's own recipe -- a release store
+// (`buffer_wbl2 sc1`, a write-back of the whole XCD L2) per publish and an
+// acquire load (`buffer_inv sc1`) per poll -- cost 517-548 us per 16.7
+// M-position MaaT round against 252 us (DESIGN.md §8c;
+// MI355X_MICROARCH.md, inter-workgroup visibility).
+template <typename T>
+__device__ inline T dev_ld(const T* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T>
+__device__ inline void dev_st(T* p, T v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // OR-reduce per contiguous segment of lanes.  `seg` is the segment id of the
 // lane (equal ids are contiguous); returns for HEAD lanes the OR of the low

@@ -22,7 +22,7 @@
 
 #include "dcc.h"
 #include "dcc_ctx.h"
-#include "dcc_device.h"
+#include "dcc_scan.h"
 #include "radix_sort.h"
 
 using namespace dcc;
@@ -72,10 +72,8 @@ __global__ __launch_bounds__(256) void k_ix_insert(const uint64_t* keys, uint64_
       }
     }
   }
-  for (int d = 32; d > 0; d >>= 1) {
-    fresh += __shfl_xor(fresh, d);
-    bad += __shfl_xor(bad, d);
-  }
+  fresh = wave_reduce<AddOp<uint32_t>>(fresh);
+  bad = wave_reduce<AddOp<uint32_t>>(bad);
   if ((threadIdx.x & 63) == 0) {
     if (fresh) atomicAdd(&cnt[0], fresh);
     if (bad) atomicAdd(&cnt[1], bad);
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(256) void k_ix_probe(const uint64_t* keys, uint64_t
     miss += r == DCC_ROW_NONE;
     out[i] = r;
   }
-  for (int d = 32; d > 0; d >>= 1) miss += __shfl_xor(miss, d);
+  miss = wave_reduce<AddOp<uint32_t>>(miss);
   if ((threadIdx.x & 63) == 0 && miss) atomicAdd(&cnt[2], miss);
 }
 
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(256) void k_wv_max(const uint32_t* wave, uint64_t n
   uint32_t m = 0;
   for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (uint64_t)gridDim.x * 256)
     m = max(m, wave[t]);
-  for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor(m, d));
+  m = wave_reduce<MaxOp<uint32_t>>(m);
   if ((threadIdx.x & 63) == 0) atomicMax(mx, m);
 }
 // sort keys: the wave of the txn at sequence position q; value: the txn

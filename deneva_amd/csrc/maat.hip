@@ -36,7 +36,7 @@
 
 #include "dcc.h"
 #include "dcc_ctx.h"
-#include "dcc_device.h"
+#include "dcc_scan.h"
 #include "dcc_env.h"
 #include "occ_kernels.h"
 #include "radix_sort.h"
@@ -112,13 +112,8 @@ __device__ inline uint32_t mt_row(MtSlot* rt, uint32_t bits, uint64_t key, bool&
 // one atomic per workgroup for a per-thread count (256 threads)
 __device__ inline void block_add(uint32_t c, uint32_t* ctr) {
   __shared__ uint32_t s_c[4];
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t v = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-    if (v) atomicAdd(ctr, v);
-  }
+  const uint32_t v = block_reduce<4, AddOp<uint32_t>>(c, s_c);
+  if (threadIdx.x == 0 && v) atomicAdd(ctr, v);
 }
 
 // rehash: every row of the old table into the new one (values carried)
@@ -304,7 +299,7 @@ __global__ __launch_bounds__(256) void k_mt_base(BaseArgs a) {
       a.sval[x] = ((uint32_t)(t0 + lo) << 2) | (rd ? SV_R : 0u) | (wr ? SV_W : 0u);
     }
   }
-  for (int d = 32; d > 0; d >>= 1) nins += __shfl_xor(nins, d);
+  nins = wave_reduce<AddOp<uint32_t>>(nins);
   if (lane == 0 && nins) atomicAdd(a.nrows, nins);
   __builtin_amdgcn_wave_barrier();
   if (lane < nt) {
@@ -379,45 +374,18 @@ struct MtRoundArgs {
   Ms* agg;
 };
 
-// wave shuffles of the four fields, then the four waves' totals through LDS
-__device__ inline Ms ms_shfl_up(const Ms& v, uint32_t d) {
-  Ms r;
-  r.flag = __shfl_up(v.flag, d);
-  r.und = __shfl_up(v.und, d);
-  r.rmax = __shfl_up(v.rmax, d);
-  r.wmin = __shfl_up(v.wmin, d);
-  return r;
-}
-__device__ inline Ms wave_incl_ms(Ms x) {
-  const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const Ms y = ms_shfl_up(x, d);
-    if (lane >= d) x = ms_comb(y, x);
+// the state as a scan operator (dcc_scan.h); not commutative.  The four
+// fields are shuffled one by one
+struct MsOp {
+  using T = Ms;
+  static constexpr bool has_inverse = false;
+  __device__ static Ms identity() { return ms_id(); }
+  __device__ static Ms combine(const Ms& a, const Ms& b) { return ms_comb(a, b); }
+  __device__ static Ms shfl_up(const Ms& v, uint32_t d) {
+    return Ms{(uint32_t)__shfl_up(v.flag, d), (uint32_t)__shfl_up(v.und, d),
+              (uint64_t)__shfl_up(v.rmax, d), (uint64_t)__shfl_up(v.wmin, d)};
   }
-  return x;
-}
-__device__ inline Ms block_reduce_ms(Ms v, Ms* s) {
-  const Ms x = wave_incl_ms(v);
-  if ((threadIdx.x & 63) == 63) s[threadIdx.x >> 6] = x;
-  __syncthreads();
-  Ms r = s[0];
-  for (uint32_t w = 1; w < 4; w++) r = ms_comb(r, s[w]);
-  __syncthreads();
-  return r;
-}
-__device__ inline Ms block_excl_ms(Ms v, Ms* s) {
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const Ms x = wave_incl_ms(v);
-  if (lane == 63) s[wv] = x;
-  __syncthreads();
-  Ms pre = ms_id();
-  for (uint32_t w = 0; w < wv; w++) pre = ms_comb(pre, s[w]);
-  Ms ex = ms_shfl_up(x, 1);
-  if (lane == 0) ex = ms_id();
-  __syncthreads();
-  return ms_comb(pre, ex);
-}
+};
 
 // A tile's flags and txns in the blocked arrangement the scans need (thread
 // t: positions 16t .. 16t + 15 of the tile), loaded with coalesced 16-B loads
@@ -483,54 +451,33 @@ struct __attribute__((aligned(64))) MtLb {
 static_assert(sizeof(MtLb) == 64, "one line per tile");
 constexpr uint32_t MT_ERR_SPIN = 8;
 
-// Every field is written and read with device-scope atomics (coherent across
-// the XCDs' L2s without a cache write-back per tile).  The status word is the
-// flag of a message-passing pair, ordered by the hardware rather than by the
-// HIP memory model's release/acquire: the payload's agent-scope stores are
-// write-through (`sc1`) and `s_waitcnt vmcnt(0)` holds the status store until
-// each of them is acknowledged at the coherence point, and a reader issues its
-// payload loads (also `sc1`, read at that point) only after the status load
-// has returned the tag (the spin's branch depends on it).  The model's own
-// recipe -- a release store (`buffer_wbl2 sc1`, a write-back of the whole XCD
-// L2) per publish and an acquire load (`buffer_inv sc1`) per poll -- is what
-// the first version of this scan used, at 517-548 us per 16.7 M-position
-// round against 252 us.
-template <typename T>
-__device__ inline void st_dev(T* p, T v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ inline T ld_dev(T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// Every field is written and read as the sc1 hand-off of dcc_device.h; the
+// status word is its flag.
 __device__ inline void mt_publish(MtLb* e, const Ms& v, bool incl, uint32_t tag) {
   if (incl) {
-    st_dev(&e->inc_rmax, v.rmax);
-    st_dev(&e->inc_wmin, v.wmin);
-    st_dev(&e->inc_fu, v.flag | (v.und << 1));
+    dev_st(&e->inc_rmax, v.rmax);
+    dev_st(&e->inc_wmin, v.wmin);
+    dev_st(&e->inc_fu, v.flag | (v.und << 1));
   } else {
-    st_dev(&e->agg_rmax, v.rmax);
-    st_dev(&e->agg_wmin, v.wmin);
-    st_dev(&e->agg_fu, v.flag | (v.und << 1));
+    dev_st(&e->agg_rmax, v.rmax);
+    dev_st(&e->agg_wmin, v.wmin);
+    dev_st(&e->agg_fu, v.flag | (v.und << 1));
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  st_dev(&e->status, (tag << 2) | (incl ? 2u : 1u));
+  vm_drain();
+  dev_st(&e->status, (tag << 2) | (incl ? 2u : 1u));
 }
 __device__ inline Ms mt_read(MtLb* e, bool incl) {
-  const uint32_t fu = ld_dev(incl ? &e->inc_fu : &e->agg_fu);
-  return Ms{fu & 1u, fu >> 1, ld_dev(incl ? &e->inc_rmax : &e->agg_rmax),
-            ld_dev(incl ? &e->inc_wmin : &e->agg_wmin)};
+  const uint32_t fu = dev_ld(incl ? &e->inc_fu : &e->agg_fu);
+  return Ms{fu & 1u, fu >> 1, dev_ld(incl ? &e->inc_rmax : &e->agg_rmax),
+            dev_ld(incl ? &e->inc_wmin : &e->agg_wmin)};
 }
 // ordered wave reduction, lane 0 rightmost: lane 0 gets v63 (x) ... (x) v0
 __device__ inline Ms wave_rcomb_ms(Ms x) {
   const uint32_t lane = threadIdx.x & 63;
 #pragma unroll
   for (uint32_t d = 1; d < 64; d <<= 1) {
-    Ms y;
-    y.flag = __shfl_down(x.flag, d);
-    y.und = __shfl_down(x.und, d);
-    y.rmax = __shfl_down(x.rmax, d);
-    y.wmin = __shfl_down(x.wmin, d);
+    const Ms y{(uint32_t)__shfl_down(x.flag, d), (uint32_t)__shfl_down(x.und, d),
+               (uint64_t)__shfl_down(x.rmax, d), (uint64_t)__shfl_down(x.wmin, d)};
     if (lane + d < 64) x = ms_comb(y, x);
   }
   return x;
@@ -563,18 +510,8 @@ __global__ __launch_bounds__(256) void k_mt_round(MtRoundArgs a, MtLb* lb, uint3
 #pragma unroll
   for (uint32_t i = 0; i < MT_ITEMS; i++) acc = ms_comb(acc, ms_elem(f[i], st[i], c[i]));
   // block exclusive prefix per thread and the tile's total
-  const Ms x = wave_incl_ms(acc);
-  if (lane == 63) s[wv] = x;
-  __syncthreads();
-  Ms pre = ms_id(), tot = ms_id();
-#pragma unroll
-  for (uint32_t w = 0; w < 4; w++) {
-    if (w < wv) pre = ms_comb(pre, s[w]);
-    tot = ms_comb(tot, s[w]);
-  }
-  Ms ex = ms_shfl_up(x, 1);
-  if (lane == 0) ex = ms_id();
-  ex = ms_comb(pre, ex);
+  Ms tot;
+  const Ms ex = block_excl<4, MsOp>(acc, s, tot);
   if (wv == 0) {
     Ms P = ms_id();
     if (tile == 0) {
@@ -587,7 +524,7 @@ __global__ __launch_bounds__(256) void k_mt_round(MtRoundArgs a, MtLb* lb, uint3
         uint32_t stw = 0;
         if (j >= 0) {
           const uint64_t t0 = spin_clock();
-          while (((stw = ld_dev(&lb[j].status)) >> 2) != tag) {
+          while (((stw = dev_ld(&lb[j].status)) >> 2) != tag) {
             __builtin_amdgcn_s_sleep(1);
             if (spin_clock() - t0 > SPIN_TICKS) {
               timed_out = true;
@@ -660,11 +597,8 @@ __global__ __launch_bounds__(256) void k_mt_decide(uint64_t n, const uint32_t* u
     uacc[t] = U64MAX;
     pend[t] = 0;
   }
-  for (int d = 32; d > 0; d >>= 1) und += __shfl_xor(und, d);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = und;
-  __syncthreads();
+  const uint32_t s = block_reduce<4, AddOp<uint32_t>>(und, sh);
   if (threadIdx.x == 0) {
-    const uint32_t s = sh[0] + sh[1] + sh[2] + sh[3];
     if (s) atomicAdd(und_out, s);
     if (blockIdx.x == 0) *und_zero = 0;
   }
@@ -726,10 +660,8 @@ __global__ __launch_bounds__(256) void k_mt_keep_count(uint64_t m, const uint8_t
       if ((f & F_LAST) && mt_keep(f, state[stx[p]])) c++;
     }
   }
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) tcnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+  c = block_reduce<4, AddOp<uint32_t>>(c, s_c);
+  if (threadIdx.x == 0) tcnt[blockIdx.x] = c;
 }
 // the kept positions of a tile, in order: blocked arrangement for the
 // prefix (loads through LDS), the kept ones staged in LDS at their tile
@@ -755,19 +687,8 @@ __global__ __launch_bounds__(256) void k_mt_keep_scatter(uint64_t m, const uint8
       c++;
     }
   // exclusive scan of c over the workgroup (thread order = position order)
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t x = c;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s_w[w] = x;
-  __syncthreads();
-  uint32_t q = x - c, tot = 0;
-  for (uint32_t v = 0; v < 4; v++) {
-    if (v < w) q += s_w[v];
-    tot += s_w[v];
-  }
+  uint32_t tot;
+  uint32_t q = block_excl<4, AddOp<uint32_t>>(c, s_w, tot);
   // stage the kept positions at their tile offsets (flags in L.f, txns in
   // L.x, slots back in s_ss once every thread holds its own)
   uint32_t sv[MT_ITEMS];
@@ -838,11 +759,9 @@ __global__ __launch_bounds__(256) void k_mt_finish(FinArgs a) {
       if (a.rw_all || ty == DCC_WR) atomicMax((unsigned long long*)&a.rt[sl].lw, c);
     }
   }
-  for (int d = 32; d > 0; d >>= 1) {
-    com += __shfl_xor(com, d);
-    und += __shfl_xor(und, d);
-    nw += __shfl_xor(nw, d);
-  }
+  com = wave_reduce<AddOp<uint32_t>>(com);
+  und = wave_reduce<AddOp<uint32_t>>(und);
+  nw = wave_reduce<AddOp<uint32_t>>(nw);
   if ((threadIdx.x & 63) == 0) {
     sh[0][threadIdx.x >> 6] = com;
     sh[1][threadIdx.x >> 6] = und;
@@ -975,7 +894,7 @@ __global__ __launch_bounds__(MS_T) void k_mt_small(const uint8_t* sfl, const uin
   __shared__ uint32_t s_pend[MS_MAXTXN];
   __shared__ Ms s_w[MS_T / 64];
   __shared__ uint32_t s_und[MS_T / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t tid = threadIdx.x;
   for (uint32_t q = tid; q < MS_MAXPOS; q += MS_T) {
     s_f[q] = q < mp ? sfl[q] : (uint8_t)0;
     s_t[q] = q < mp ? (uint16_t)stx[q] : (uint16_t)0;
@@ -1000,14 +919,8 @@ __global__ __launch_bounds__(MS_T) void k_mt_small(const uint8_t* sfl, const uin
       const uint8_t st = (f & F_LAST) ? s_st[tx] : ST_ABO;
       acc = ms_comb(acc, ms_elem(f, st, st == ST_COM ? (uint64_t)s_cts[tx] : 0));
     }
-    const Ms x = wave_incl_ms(acc);
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    Ms pre = ms_id();
-    for (uint32_t w = 0; w < wv; w++) pre = ms_comb(pre, s_w[w]);
-    Ms ex = ms_shfl_up(x, 1);
-    if (lane == 0) ex = ms_id();
-    Ms run = ms_comb(pre, ex);
+    Ms wtot;
+    Ms run = block_excl<MS_T / 64, MsOp>(acc, s_w, wtot);
     for (uint32_t i = 0; i < MS_ITEMS; i++) {
       if (tid * MS_ITEMS + i >= mp) break;
       const uint8_t f = s_f[tid * MS_ITEMS + i];
@@ -1038,11 +951,7 @@ __global__ __launch_bounds__(MS_T) void k_mt_small(const uint8_t* sfl, const uin
       s_u[tid] = U64MAX;
       s_pend[tid] = 0;
     }
-    for (int d = 32; d > 0; d >>= 1) und += __shfl_xor(und, d);
-    if (lane == 0) s_und[wv] = und;
-    __syncthreads();
-    uint32_t tot = 0;
-    for (uint32_t w = 0; w < MS_T / 64; w++) tot += s_und[w];
+    const uint32_t tot = block_reduce<MS_T / 64, AddOp<uint32_t>>(und, s_und);
     if (tot == 0 || r > P + 8) break;  // uniform; the smallest undecided txn decides every round
     __syncthreads();  // s_w / s_und of the next round
   }
@@ -1071,10 +980,8 @@ __global__ __launch_bounds__(256) void k_mt_gcount(const uint32_t* off, uint64_t
   __shared__ uint32_t sh[4];
   const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   uint32_t c = mt_keep_len(off, n, state, t);
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  c = block_reduce<4, AddOp<uint32_t>>(c, sh);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = c;
 }
 __global__ __launch_bounds__(256) void k_mt_gscatter(const uint32_t* off, uint64_t n, const uint8_t* state,
                                                      const uint8_t* at, uint32_t rw_all, const uint32_t* slot,
@@ -1084,11 +991,7 @@ __global__ __launch_bounds__(256) void k_mt_gscatter(const uint32_t* off, uint64
   const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const uint32_t len = mt_keep_len(off, n, state, t);
   const uint32_t o0 = t < n ? off[t] : 0u;
-  uint32_t x = len;  // inclusive prefix of the wave's kept lengths
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
+  const uint32_t x = wave_incl<AddOp<uint32_t>>(len);  // inclusive prefix of the wave's kept lengths
   if (lane == 63) sh[wv] = x;
   __syncthreads();
   uint32_t b = bsum[blockIdx.x];

@@ -14,6 +14,7 @@
 
 #include "dcc_device.h"
 #include "dcc_env.h"
+#include "dcc_scan.h"
 #include "occ_history.h"
 #include "occ_kernels.h"
 #include "radix_sort.h"
@@ -35,37 +36,15 @@ __device__ inline uint32_t hist_writes_of(uint64_t t, const uint32_t* off, const
   return c;
 }
 
-// exclusive scan over the block (1024 threads = 16 waves); returns the block total
-__device__ inline uint32_t block_excl_scan1024(uint32_t v, uint32_t& excl) {
-  __shared__ uint32_t s_w[HB / 64];
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s_w[w] = x;
-  __syncthreads();
-  uint32_t before = 0, total = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < HB / 64; q++) {
-    const uint32_t s = s_w[q];
-    if (q < w) before += s;
-    total += s;
-  }
-  excl = before + x - v;
-  return total;
-}
-
 __global__ __launch_bounds__(HB) void k_hist_count(uint64_t n, const uint32_t* off,
                                                    const uint8_t* acctype, uint64_t nnz,
                                                    const uint64_t* tn, uint32_t* bsum) {
+  __shared__ uint32_t s_w[HB / 64];
   const uint64_t t = (uint64_t)blockIdx.x * HB + threadIdx.x;
   uint32_t a0;
   const uint32_t c = t < n ? hist_writes_of(t, off, acctype, nnz, tn, a0) : 0u;
-  uint32_t ex;
-  const uint32_t tot = block_excl_scan1024(c, ex);
+  uint32_t tot;
+  (void)block_excl<HB / 64, AddOp<uint32_t>>(c, s_w, tot);
   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -75,11 +54,12 @@ __global__ __launch_bounds__(HB) void k_hist_emit(uint64_t n, const uint32_t* of
                                                   const uint32_t* bsum, uint64_t* out_k,
                                                   uint64_t* out_t, unsigned long long* kmax) {
   __shared__ unsigned long long s_mx;
+  __shared__ uint32_t s_w[HB / 64];
   const uint64_t t = (uint64_t)blockIdx.x * HB + threadIdx.x;
   uint32_t a0 = 0;
   const uint32_t c = t < n ? hist_writes_of(t, off, acctype, nnz, tn, a0) : 0u;
-  uint32_t ex;
-  (void)block_excl_scan1024(c, ex);
+  uint32_t tot;
+  const uint32_t ex = block_excl<HB / 64, AddOp<uint32_t>>(c, s_w, tot);
   if (threadIdx.x == 0) s_mx = 0;
   __syncthreads();
   uint64_t mx = 0;
@@ -95,7 +75,7 @@ __global__ __launch_bounds__(HB) void k_hist_emit(uint64_t n, const uint32_t* of
       p++;
     }
   }
-  for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint64_t)__shfl_xor(mx, d));
+  mx = wave_reduce<MaxOp<uint64_t>>(mx);
   if ((threadIdx.x & 63) == 0 && mx) atomicMax(&s_mx, (unsigned long long)mx);
   __syncthreads();
   if (threadIdx.x == 0 && s_mx) atomicMax(kmax, s_mx);  // one per workgroup
@@ -113,9 +93,8 @@ __global__ __launch_bounds__(HB) void k_hist_emit(uint64_t n, const uint32_t* of
 // contention) read their access lists.
 //
 // Look-back words, as MaaT's round scan (maat.hip): payload and status are
-// written with device-scope atomics, the status after `s_waitcnt vmcnt(0)`
-// (the payload is at the coherence point first), and read in the other
-// order; the status carries the epoch's tag (dyn->fin_tag), so nothing is
+// the sc1 hand-off of dcc_device.h (dev_st, vm_drain, dev_st; read in the
+// other order); the status carries the epoch's tag (dyn->fin_tag), so nothing is
 // reset between epochs.
 struct __attribute__((aligned(64))) FinLb {
   uint64_t agg, inc;  // commits | writes << 32: the workgroup's, and through it
@@ -132,18 +111,10 @@ struct FinTail {
   uint32_t pad[10];
 };
 static_assert(sizeof(FinTail) == 64, "one line");
-template <typename T>
-__device__ inline void fin_st(T* p, T v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ inline T fin_ld(T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ inline void fin_publish(FinLb* e, uint64_t v, bool incl, uint32_t tag) {
-  fin_st(incl ? &e->inc : &e->agg, v);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  fin_st(&e->status, (tag << 2) | (incl ? 2u : 1u));
+  dev_st(incl ? &e->inc : &e->agg, v);
+  vm_drain();
+  dev_st(&e->status, (tag << 2) | (incl ? 2u : 1u));
 }
 
 // A committed writer's accesses [o0, o1), FIN_U at a time: every type and
@@ -186,46 +157,12 @@ __device__ inline uint32_t fin_writes(uint64_t t, const OccFinArgs& a, uint64_t&
   return c;
 }
 
-// block-wide exclusive scans of two counters (FB threads); returns both totals
-template <uint32_t FB>
-__device__ inline void block_excl_scan2(uint32_t v0, uint32_t v1, uint32_t& e0, uint32_t& e1,
-                                        uint32_t& t0, uint32_t& t1) {
-  __shared__ uint32_t s_w[2][FB / 64];
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t x0 = v0, x1 = v1;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y0 = __shfl_up(x0, d), y1 = __shfl_up(x1, d);
-    if (lane >= (uint32_t)d) {
-      x0 += y0;
-      x1 += y1;
-    }
-  }
-  if (lane == 63) {
-    s_w[0][w] = x0;
-    s_w[1][w] = x1;
-  }
-  __syncthreads();
-  uint32_t b0 = 0, b1 = 0;
-  t0 = t1 = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < FB / 64; q++) {
-    if (q < w) {
-      b0 += s_w[0][q];
-      b1 += s_w[1][q];
-    }
-    t0 += s_w[0][q];
-    t1 += s_w[1][q];
-  }
-  e0 = b0 + x0 - v0;
-  e1 = b1 + x1 - v1;
-}
-
 template <uint32_t FB, uint32_t FIN_T>
 __global__ __launch_bounds__(FB, 8) void k_fin(OccFinArgs a) {
   __shared__ unsigned long long s_mx;
   __shared__ uint64_t s_pre;
   __shared__ uint32_t s_last, s_id;
+  __shared__ uint64_t s_w[FB / 64];
   const OccDyn* dy = a.dyn;
   const uint32_t tag = a.tag ? a.tag : dy->fin_tag;
   const bool chained = a.ctl != nullptr;
@@ -271,13 +208,15 @@ __global__ __launch_bounds__(FB, 8) void k_fin(OccFinArgs a) {
     if (chained && t_0 + i < a.n) und += a.state[t_0 + i] == ST_UNDECIDED;
   }
   if (chained) {  // the epoch's undecided txns, one atomic per wave (none usually)
-    for (int d = 32; d > 0; d >>= 1) und += __shfl_xor(und, d);
+    und = wave_reduce<AddOp<uint32_t>>(und);
     if ((threadIdx.x & 63) == 0 && und) atomicAdd(&tail->und, und);
   }
   if (threadIdx.x == 0) s_mx = 0;
-  uint32_t e0, e1, t0, t1;
-  block_excl_scan2<FB>(cs, ws, e0, e1, t0, t1);  // its barrier orders s_mx's reset
-  for (int d = 32; d > 0; d >>= 1) kmx = max(kmx, (uint64_t)__shfl_xor(kmx, d));
+  // commits | writes << 32 in one scan (neither sum reaches 2^32); its barrier orders s_mx's reset
+  uint64_t tt;
+  const uint64_t ee = block_excl<FB / 64, AddOp<uint64_t>>((uint64_t)cs | ((uint64_t)ws << 32), s_w, tt);
+  const uint32_t e0 = (uint32_t)ee, e1 = (uint32_t)(ee >> 32), t0 = (uint32_t)tt, t1 = (uint32_t)(tt >> 32);
+  kmx = wave_reduce<MaxOp<uint64_t>>(kmx);
   if ((threadIdx.x & 63) == 0 && kmx) atomicMax(&s_mx, (unsigned long long)kmx);
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -296,7 +235,7 @@ __global__ __launch_bounds__(FB, 8) void k_fin(OccFinArgs a) {
         uint32_t stw = 0;
         if (j >= 0) {
           const uint64_t t0 = spin_clock();
-          while (((stw = fin_ld(&lb[j].status)) >> 2) != tag) {
+          while (((stw = dev_ld(&lb[j].status)) >> 2) != tag) {
             __builtin_amdgcn_s_sleep(1);
             if (spin_clock() - t0 > SPIN_TICKS) {  // dispatch is in index order: a hang, not a wait
               timed_out = true;
@@ -311,9 +250,8 @@ __global__ __launch_bounds__(FB, 8) void k_fin(OccFinArgs a) {
         const bool inc = j >= 0 && (stw & 3u) == 2u;
         const uint64_t im = ballot64(inc);
         const uint32_t stop = im ? (uint32_t)__builtin_ctzll(im) : 63u;
-        uint64_t v = (j >= 0 && lane <= stop) ? fin_ld(inc ? &lb[j].inc : &lb[j].agg) : 0ull;
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        P += v;
+        uint64_t v = (j >= 0 && lane <= stop) ? dev_ld(inc ? &lb[j].inc : &lb[j].agg) : 0ull;
+        P += wave_reduce<AddOp<uint64_t>>(v);
         if (im) break;
       }
       if (lane == 0) fin_publish(&lb[bid], P == ~0ull ? ~0ull : P + tot, true, tag);
@@ -363,12 +301,12 @@ __global__ __launch_bounds__(FB, 8) void k_fin(OccFinArgs a) {
   // the last workgroup to finish: totals to pinned memory (every value it
   // reads was written with device-scope atomics, acknowledged before the
   // writer's arrival)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_drain();
   __syncthreads();
   if (threadIdx.x == 0) s_last = atomicAdd(&tail->done, 1u) == gridDim.x - 1;
   __syncthreads();
   if (s_last && threadIdx.x == 0) {
-    const uint64_t g = fin_ld(&lb[gridDim.x - 1].inc);
+    const uint64_t g = dev_ld(&lb[gridDim.x - 1].inc);
     a.totals[0] = g == ~0ull ? ~0ull : (uint32_t)g;
     a.totals[1] = g >> 32;
     a.totals[2] = atomicExch(&tail->kmax, 0ull);
@@ -376,19 +314,19 @@ __global__ __launch_bounds__(FB, 8) void k_fin(OccFinArgs a) {
     if (chained) {
       // the epoch is final and numbered from the snapshot: the next one in
       // submit order may go on from here
-      const bool ok = g != ~0ull && fin_ld(&tail->und) == 0 && fin_ld(&tail->capx) == 0 &&
-                      (fin_ld(a.err) & ERR_NOT_FINAL) == 0 && (!a.wfull || fin_ld(a.wfull) == 0);
+      const bool ok = g != ~0ull && dev_ld(&tail->und) == 0 && dev_ld(&tail->capx) == 0 &&
+                      (dev_ld(a.err) & ERR_NOT_FINAL) == 0 && (!a.wfull || dev_ld(a.wfull) == 0);
       if (ok) {
-        fin_st(&a.ctl->tnc, dy->tnc + (uint32_t)g);
-        fin_st(&a.ctl->hist_m, dy->hist_m + (g >> 32));
+        dev_st(&a.ctl->tnc, dy->tnc + (uint32_t)g);
+        dev_st(&a.ctl->hist_m, dy->hist_m + (g >> 32));
         __hip_atomic_store(&a.ctl->seq, a.seq + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       }
       a.totals[4] = ok ? 1u : 0u;
-      fin_st(&tail->und, 0u);
-      fin_st(&tail->capx, 0u);
+      dev_st(&tail->und, 0u);
+      dev_st(&tail->capx, 0u);
     }
-    fin_st(&tail->ticket, 0u);  // every workgroup took its ticket before it arrived
-    fin_st(&tail->done, 0u);
+    dev_st(&tail->ticket, 0u);  // every workgroup took its ticket before it arrived
+    dev_st(&tail->done, 0u);
   }
 }
 
@@ -404,15 +342,15 @@ __global__ __launch_bounds__(256) void k_fin_prep(const uint32_t* src, OccDyn* d
     const uint64_t s = __hip_atomic_load(&ctl->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
     const bool at = s == seq;
     if (at) {
-      dyn->tnc = fin_ld(&ctl->tnc);
-      dyn->hist_m = fin_ld(&ctl->hist_m);
+      dyn->tnc = dev_ld(&ctl->tnc);
+      dyn->hist_m = dev_ld(&ctl->hist_m);
     }
     dyn->pad = at ? 1u : 0u;
   }
 }
 __global__ void k_fin_ctl_set(FinCtl* ctl, uint64_t tnc, uint64_t hist_m, uint64_t seq) {
-  fin_st(&ctl->tnc, tnc);
-  fin_st(&ctl->hist_m, hist_m);
+  dev_st(&ctl->tnc, tnc);
+  dev_st(&ctl->hist_m, hist_m);
   __hip_atomic_store(&ctl->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 

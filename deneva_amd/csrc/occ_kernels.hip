@@ -805,7 +805,7 @@ __global__ __launch_bounds__(256) void k_decide(uint8_t* __restrict__ state,
       gst[t] = 0;
     }
   }
-  const uint32_t tot = block_sum_u32(cnt, sh);
+  const uint32_t tot = block_reduce_reuse<AddOp<uint32_t>>(cnt, sh, blockDim.x >> 6);
   if (threadIdx.x == 0 && tot) atomicAdd(und, tot);
 }
 
@@ -854,9 +854,11 @@ __global__ __launch_bounds__(256) void k_final(FinalArgs a, GatherArgs g) {
     a.rc[t] = st == ST_COMMIT ? 0 /* RCOK */ : 2 /* Abort */;
     if (a.cflag) a.cflag[t] = f;
   }
-  const uint32_t s0 = block_sum_u32(c, sh), s1 = block_sum_u32(ab, sh),
-                 s2 = block_sum_u32(ro, sh), s3 = block_sum_u32(cw, sh),
-                 s4 = block_sum_u32(und, sh);
+  using Sum = AddOp<uint32_t>;
+  const uint32_t nwv = blockDim.x >> 6;
+  const uint32_t s0 = block_reduce_reuse<Sum>(c, sh, nwv), s1 = block_reduce_reuse<Sum>(ab, sh, nwv),
+                 s2 = block_reduce_reuse<Sum>(ro, sh, nwv), s3 = block_reduce_reuse<Sum>(cw, sh, nwv),
+                 s4 = block_reduce_reuse<Sum>(und, sh, nwv);
   if (threadIdx.x == 0) a.part[blockIdx.x] = FinalPart{s0, s1, s2, s3, s4, 0, 0, 0};
 }
 
@@ -866,15 +868,8 @@ __global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t* __restrict
                                                       uint64_t* __restrict__ bsum) {
   __shared__ uint32_t s[16];
   const uint64_t t = (uint64_t)blockIdx.x * 1024 + threadIdx.x;
-  uint32_t v = t < n ? f[t] : 0;
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t tot = 0;
-    for (int w = 0; w < 16; w++) tot += s[w];
-    bsum[blockIdx.x] = tot;
-  }
+  const uint32_t tot = block_reduce<16, AddOp<uint32_t>>(t < n ? f[t] : 0u, s);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
 // exclusive scan of the block sums in place: one workgroup, 1024 sums per
@@ -882,24 +877,16 @@ __global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t* __restrict
 __global__ __launch_bounds__(1024) void k_scan_sums(uint64_t* __restrict__ bsum, uint64_t nb) {
   __shared__ uint64_t s_w[16];
   __shared__ uint64_t s_carry;
-  const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
   if (threadIdx.x == 0) s_carry = 0;
   __syncthreads();
   for (uint64_t c0 = 0; c0 < nb; c0 += 1024) {
     const uint64_t q = c0 + threadIdx.x;
     const uint64_t v = q < nb ? bsum[q] : 0ull;
-    uint64_t x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(x, d);
-      if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint64_t base = s_carry;
-    for (uint32_t w = 0; w < wv; w++) base += s_w[w];
-    if (q < nb) bsum[q] = base + x - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) s_carry = base + x;
+    uint64_t total;
+    const uint64_t ex = s_carry + block_excl<16, AddOp<uint64_t>>(v, s_w, total);
+    if (q < nb) bsum[q] = ex;
+    __syncthreads();  // s_carry and s_w read by every thread
+    if (threadIdx.x == 1023) s_carry = ex + v;
     __syncthreads();
   }
 }
@@ -910,18 +897,9 @@ __global__ __launch_bounds__(1024) void k_scan_apply(const uint32_t* __restrict_
   __shared__ uint32_t s[16];
   const uint64_t t = (uint64_t)blockIdx.x * 1024 + threadIdx.x;
   const uint32_t v = t < n ? f[t] : 0;
-  // inclusive wave scan
-  uint32_t x = v;
-  const uint32_t lane = lane_id();
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s[threadIdx.x >> 6] = x;
-  __syncthreads();
-  uint32_t woff = 0;
-  for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) woff += s[w];
-  if (t < n) tn[t] = v ? tnc + bsum[blockIdx.x] + woff + x : 0;
+  uint32_t total;
+  const uint32_t ex = block_excl<16, AddOp<uint32_t>>(v, s, total);
+  if (t < n) tn[t] = v ? tnc + bsum[blockIdx.x] + ex + v : 0;  // inclusive rank
 }
 
 // --------------------------------------------------------------------------
@@ -1029,7 +1007,8 @@ __global__ __launch_bounds__(256) void k_finish_flags(const uint8_t* __restrict_
     c += f;
     bad += (g && !local) ? 1u : 0u;
   }
-  const uint32_t sc = block_sum_u32(c, sh), sb = block_sum_u32(bad, sh);
+  const uint32_t sc = block_reduce_reuse<AddOp<uint32_t>>(c, sh, blockDim.x >> 6),
+                 sb = block_reduce_reuse<AddOp<uint32_t>>(bad, sh, blockDim.x >> 6);
   if (threadIdx.x == 0) {
     if (sc) atomicAdd(&cnt[0], sc);
     if (sb) atomicAdd(&cnt[1], sb);

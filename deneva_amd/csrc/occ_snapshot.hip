@@ -29,7 +29,7 @@
 
 #include "dcc.h"
 #include "dcc_ctx.h"
-#include "dcc_device.h"
+#include "dcc_scan.h"
 #include "occ_kernels.h"
 
 using namespace dcc;
@@ -292,13 +292,11 @@ __global__ __launch_bounds__(256) void k_snap(SnapArgs a) {
   uint64_t v1 = c.n_commit, v2 = c.n_ro, v3 = c.n_w;
   uint32_t err = c.err;
   uint64_t bytes = c.bytes;
-  for (int m = 32; m >= 1; m >>= 1) {
-    bytes += __shfl_xor(bytes, m);
-    v1 += __shfl_xor(v1, m);
-    v2 += __shfl_xor(v2, m);
-    v3 += __shfl_xor(v3, m);
-    err |= __shfl_xor(err, m);
-  }
+  bytes = wave_reduce<AddOp<uint64_t>>(bytes);
+  v1 = wave_reduce<AddOp<uint64_t>>(v1);
+  v2 = wave_reduce<AddOp<uint64_t>>(v2);
+  v3 = wave_reduce<AddOp<uint64_t>>(v3);
+  err = wave_reduce<OrOp<uint32_t>>(err);
   if (lane < SNAP_NCNT) {  // every wave of the grid writes its row
     const unsigned long long v[SNAP_NCNT] = {err, v1, v2, v3, bytes};
     unsigned long long x = v[0];

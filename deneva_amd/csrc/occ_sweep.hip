@@ -200,37 +200,6 @@ __device__ inline void range_set(uint64_t* bm, uint32_t lo, uint32_t len) {
   }
 }
 
-__device__ inline uint64_t wave_or64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v |= __shfl_xor(v, d);
-  return v;
-}
-__device__ inline uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ inline uint32_t wave_max32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor(v, d));
-  return v;
-}
-__device__ inline uint32_t wave_excl_u32(uint32_t v, uint32_t& total) {
-  const uint32_t lane = lane_id();
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  total = __shfl(x, 63);
-  return x - v;
-}
-__device__ inline uint64_t lanemask_lt() {
-  const uint32_t l = lane_id();
-  return l ? (~0ull >> (64 - l)) : 0ull;
-}
-
 __device__ inline uint32_t list_len(const uint32_t* m_dev, uint32_t m_host) {
   return m_dev ? *m_dev : m_host;
 }
@@ -620,7 +589,7 @@ __global__ __launch_bounds__(256) void k_sw_rows(SwPreArgs a) {
   if (wv == 0) {
     const uint32_t vp = lane < nch ? s_cp[lane] : 0u, vi = lane < nch ? s_ci[lane] : 0u;
     uint32_t tp, ti;
-    const uint32_t ep = wave_excl_u32(vp, tp), ei = wave_excl_u32(vi, ti);
+    const uint32_t ep = wave_excl<AddOp<uint32_t>>(vp, tp), ei = wave_excl<AddOp<uint32_t>>(vi, ti);
     if (lane < nch) {
       s_cp[lane] = ep;
       s_ci[lane] = ei;
@@ -1252,7 +1221,7 @@ __global__ __launch_bounds__(SW_CHUNK, DCC_F_WPE) void k_sw_filter(SwFilterArgs 
     bool pref = false;
     const uint64_t vm = ballot64(valid);
     const uint32_t A0 = vm ? __shfl(s, 0) : 0u;
-    const uint32_t A1 = wave_max32(valid ? e : 0u);
+    const uint32_t A1 = wave_reduce<MaxOp<uint32_t>>(valid ? e : 0u);
     uint32_t span = A1 > A0 ? A1 - A0 : 0u;
     if (span > SW_WA) {  // malformed offsets (the host reports them): skip
       if (lane == 0) atomicOr(a.err, ERR_TILE);
@@ -1311,7 +1280,7 @@ __global__ __launch_bounds__(SW_CHUNK, DCC_F_WPE) void k_sw_filter(SwFilterArgs 
       {
         const uint32_t pw = lane < nw ? (uint32_t)__popcll(hit[lane]) : 0u;
         uint32_t ptot;
-        const uint32_t pre = wave_excl_u32(pw, ptot);
+        const uint32_t pre = wave_excl<AddOp<uint32_t>>(pw, ptot);
         if (lane < nw) s_wpre[wv][lane] = pre;
       }
       // Bloom-positive accesses of the txn, verified one by one (almost always
@@ -1342,7 +1311,7 @@ __global__ __launch_bounds__(SW_CHUNK, DCC_F_WPE) void k_sw_filter(SwFilterArgs 
     if (cand && ok && rlen == 0) a.state[tid] = ST_COMMIT;  // no keys: nothing can kill it
     const bool surv = cand && ok && rlen && !killed;
     const uint64_t sm = ballot64(surv);
-    const uint64_t acc = wave_sum64(surv ? rlen : 0u);
+    const uint64_t acc = wave_reduce<AddOp<uint64_t>>(surv ? rlen : 0u);
     const uint64_t cnt = ((uint64_t)__popcll(sm) << LB_ACC_BITS) | acc;
     wsum += cnt;
     if (lane == 0) {
@@ -1351,7 +1320,7 @@ __global__ __launch_bounds__(SW_CHUNK, DCC_F_WPE) void k_sw_filter(SwFilterArgs 
     }
     if (a.ro_split) {  // read-only survivors, counted apart (k_sw_compact splits them off)
       const uint64_t rm = ballot64(surv && ro);
-      const uint64_t racc = wave_sum64(surv && ro ? rlen : 0u);
+      const uint64_t racc = wave_reduce<AddOp<uint64_t>>(surv && ro ? rlen : 0u);
       const uint64_t rc = ((uint64_t)__popcll(rm) << LB_ACC_BITS) | racc;
       rsum += rc;
       if (lane == 0) {
@@ -1426,7 +1395,7 @@ __global__ __launch_bounds__(SW_CHUNK) void k_sw_apply(SwFilterArgs a) {
       ro = a.ro_split && a.hasw[tid] == 0;  // the has-write bytes are the whole batch's
     }
     const uint64_t sm = ballot64(surv);
-    const uint64_t acc = wave_sum64(surv ? len : 0u);
+    const uint64_t acc = wave_reduce<AddOp<uint64_t>>(surv ? len : 0u);
     const uint64_t cnt = ((uint64_t)__popcll(sm) << LB_ACC_BITS) | acc;
     wsum += cnt;
     if (lane == 0) {
@@ -1435,7 +1404,7 @@ __global__ __launch_bounds__(SW_CHUNK) void k_sw_apply(SwFilterArgs a) {
     }
     if (a.ro_split) {  // read-only survivors counted apart (as the filter does)
       const uint64_t rm = ballot64(surv && ro);
-      const uint64_t racc = wave_sum64(surv && ro ? len : 0u);
+      const uint64_t racc = wave_reduce<AddOp<uint64_t>>(surv && ro ? len : 0u);
       const uint64_t rc = ((uint64_t)__popcll(rm) << LB_ACC_BITS) | racc;
       rsum += rc;
       if (lane == 0) {
@@ -1471,7 +1440,7 @@ __global__ __launch_bounds__(SG_T) void k_sw_sg_scan(const uint32_t* tid, const 
                                                      uint32_t* err) {
   __shared__ uint32_t s_w[SG_T / 64];
   __shared__ uint32_t s_carry;
-  const uint32_t P = min(p_max, *m_dev), lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t P = min(p_max, *m_dev);
   if (threadIdx.x == 0) s_carry = 0;
   __syncthreads();
   for (uint32_t q0 = 0; q0 < P; q0 += SG_T) {
@@ -1486,18 +1455,11 @@ __global__ __launch_bounds__(SG_T) void k_sw_sg_scan(const uint32_t* tid, const 
         len = 0;
       }
     }
-    uint32_t x = len;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d);
-      if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint32_t b = s_carry;
-    for (uint32_t w = 0; w < wv; w++) b += s_w[w];
-    if (q < P) soff[q] = b + x - len;
-    __syncthreads();
-    if (threadIdx.x == SG_T - 1) s_carry = b + x;
+    uint32_t tot;
+    const uint32_t ex = s_carry + block_excl<SG_T / 64, AddOp<uint32_t>>(len, s_w, tot);
+    if (q < P) soff[q] = ex;
+    __syncthreads();  // s_carry and s_w read by every thread
+    if (threadIdx.x == SG_T - 1) s_carry = ex + len;
     __syncthreads();
   }
   if (threadIdx.x == 0) soff[P] = s_carry;
@@ -1570,7 +1532,7 @@ __global__ __launch_bounds__(1024) void k_sw_mscan(uint32_t* cnt, uint32_t P, ui
     const uint32_t t = c0 + j;
     const uint32_t v = t < P ? cnt[t] : 0u;
     uint32_t tot;
-    const uint32_t ex = wave_excl_u32(v, tot);
+    const uint32_t ex = wave_excl<AddOp<uint32_t>>(v, tot);
     if (lane == 0) s_w[wv] = tot;
     __syncthreads();
     uint32_t base = s_carry;
@@ -1657,10 +1619,10 @@ __global__ __launch_bounds__(SW_CHUNK) void k_sw_compact(SwFilterArgs a) {
         }
       }
     }
-    pre = wave_sum64(pre);
-    all = wave_sum64(all);
-    rpre = wave_sum64(rpre);
-    rall = wave_sum64(rall);
+    pre = wave_reduce<AddOp<uint64_t>>(pre);
+    all = wave_reduce<AddOp<uint64_t>>(all);
+    rpre = wave_reduce<AddOp<uint64_t>>(rpre);
+    rall = wave_reduce<AddOp<uint64_t>>(rall);
     if (lane == 0) {
       s_part[wv][0] = pre;
       s_part[wv][1] = all;
@@ -1704,14 +1666,10 @@ __global__ __launch_bounds__(SW_CHUNK) void k_sw_compact(SwFilterArgs a) {
     for (uint32_t c0 = t_lo; c0 < t_hi; c0 += 64) {
       const uint32_t q = c0 + lane;
       const uint64_t v = (q < t_hi ? a.tcount[q] : 0ull) - ((split && q < t_hi) ? a.rtcount[q] : 0ull);
-      uint64_t x = v;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
-      }
-      if (q < t_hi) s_tb[q - t_lo] = run + x - v;
-      run += __shfl(x, 63);
+      uint64_t tot;
+      const uint64_t ex = wave_excl<AddOp<uint64_t>>(v, tot);
+      if (q < t_hi) s_tb[q - t_lo] = run + ex;
+      run += tot;
     }
   }
   __syncthreads();
@@ -1758,7 +1716,7 @@ __global__ __launch_bounds__(SW_CHUNK) void k_sw_compact(SwFilterArgs a) {
         len = (uint32_t)min((uint64_t)ev[i], nnz) - s;
       }
       uint32_t atot;
-      const uint32_t aex = wave_excl_u32(len, atot);
+      const uint32_t aex = wave_excl<AddOp<uint32_t>>(len, atot);
       if (surv) {
         const uint32_t r = tb + (uint32_t)__popcll(word & lanemask_lt());
         a.tid_out[r] = tv[i];

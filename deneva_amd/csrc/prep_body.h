@@ -6,29 +6,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dcc_scan.h"
 #include "occ_kernels.h"
 
 namespace dcc {
-
-// block reductions for workgroups of up to 16 waves (sh: 16 words)
-__device__ inline uint32_t block_sum_u32(uint32_t v, uint32_t* sh) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t t = 0;
-  for (uint32_t w = 0; w < (blockDim.x >> 6); w++) t += sh[w];
-  return t;
-}
-__device__ inline uint32_t block_max_u32(uint32_t v, uint32_t* sh) {
-  for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor(v, d));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t t = 0;
-  for (uint32_t w = 0; w < (blockDim.x >> 6); w++) t = max(t, sh[w]);
-  return t;
-}
 
 // workgroup `blk` of `nblk` (every thread of the workgroup calls it)
 __device__ inline void prep_body(const uint32_t* __restrict__ off, uint64_t n, const uint8_t* __restrict__ at,
@@ -68,10 +49,11 @@ __device__ inline void prep_body(const uint32_t* __restrict__ off, uint64_t n, c
       }
     }
   }
-  const uint32_t tl = block_max_u32(len, sh);
-  const uint32_t tb = block_max_u32(bad, sh);  // error bits are 0/1 flags: max == or here
-  const uint32_t tw = block_sum_u32(nw, sh);
-  const uint32_t tp = block_sum_u32(nwp, sh);
+  const uint32_t nwv = blockDim.x >> 6;
+  const uint32_t tl = block_reduce_reuse<MaxOp<uint32_t>>(len, sh, nwv);
+  const uint32_t tb = block_reduce_reuse<MaxOp<uint32_t>>(bad, sh, nwv);  // error bits are 0/1 flags: max == or here
+  const uint32_t tw = block_reduce_reuse<AddOp<uint32_t>>(nw, sh, nwv);
+  const uint32_t tp = block_reduce_reuse<AddOp<uint32_t>>(nwp, sh, nwv);
   if (threadIdx.x == 0) part[blk] = PrepPart{tb, tl, tw, tp};
 }
 
@@ -114,9 +96,10 @@ __device__ inline void prep_body_hasw(const uint32_t* __restrict__ off, uint64_t
     nw += c;
     hasw[t] = c ? 1 : 0;
   }
-  const uint32_t tl = block_max_u32(len, sh);
-  const uint32_t tb = block_max_u32(bad, sh);
-  const uint32_t tw = block_sum_u32(nw, sh);
+  const uint32_t nwv = blockDim.x >> 6;
+  const uint32_t tl = block_reduce_reuse<MaxOp<uint32_t>>(len, sh, nwv);
+  const uint32_t tb = block_reduce_reuse<MaxOp<uint32_t>>(bad, sh, nwv);
+  const uint32_t tw = block_reduce_reuse<AddOp<uint32_t>>(nw, sh, nwv);
   if (threadIdx.x == 0) {
     part[blk] = PrepPart{tb, tl, tw, 0u};
     if (errw && ((tb & ERR_OFFSETS) || tl > MAX_TXN_LEN)) atomicOr(errw, ERR_PREP);

@@ -5,6 +5,7 @@
 
 #include "dcc_device.h"
 #include "dcc_env.h"
+#include "dcc_scan.h"
 #include "radix_sort.h"
 
 namespace dcc {
@@ -20,35 +21,8 @@ __device__ inline uint64_t digit_peers(uint32_t d, bool act) {
   return act ? m : 0ull;
 }
 
-__device__ inline uint64_t lanemask_lt() {
-  const uint32_t l = lane_id();
-  return l == 0 ? 0ull : (~0ull >> (64 - l));
-}
-
 constexpr uint32_t RS_W = RS_THREADS / 64;  // waves per workgroup
 static_assert(RS_THREADS >= 256, "one thread per digit");
-
-// Exclusive scan of one u32 per thread over the workgroup.
-__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* sh /*[RS_W]*/, uint32_t& total) {
-  const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  __syncthreads();
-  if (lane == 63) sh[wv] = x;
-  __syncthreads();
-  uint32_t off = 0;
-  total = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < RS_W; w++) {
-    if (w < wv) off += sh[w];
-    total += sh[w];
-  }
-  return off + x - v;
-}
 
 // Per-tile digit counts: one LDS histogram per wave, summed at the end.
 // Thread t counts the tile's items [16t, 16t + 16) (16-B loads): a run of
@@ -120,7 +94,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scan(uint32_t* __restrict__ c
       s += v[q];
     }
     uint32_t total;
-    uint32_t pre = run + block_excl_scan(s, sh, total);
+    uint32_t pre = run + block_excl_reuse<RS_W, AddOp<uint32_t>>(s, sh, total);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const uint32_t i = c0 + threadIdx.x * 4 + q;
@@ -171,7 +145,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const K* __restrict__
   }
   {
     uint32_t total;
-    const uint32_t g = block_excl_scan(dig ? tot[tid] : 0u, sh, total);
+    const uint32_t g = block_excl_reuse<RS_W, AddOp<uint32_t>>(dig ? tot[tid] : 0u, sh, total);
     if (dig) s_gb[tid] = g + cnt[(uint64_t)tid * tiles + blockIdx.x];
   }
   for (uint32_t q = tid; q < W * 256; q += RS_THREADS) (&s_wc[0][0])[q] = 0;
@@ -202,7 +176,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const K* __restrict__
       t += c[w];
     }
     uint32_t total;
-    uint32_t b = block_excl_scan(t, sh, total);
+    uint32_t b = block_excl_reuse<RS_W, AddOp<uint32_t>>(t, sh, total);
     __syncthreads();  // every wave's counts read before they become bases
     if (dig) {
       s_tb[tid] = b;

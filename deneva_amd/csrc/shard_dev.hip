@@ -16,7 +16,7 @@
 
 #include "dcc.h"
 #include "dcc_ctx.h"
-#include "dcc_device.h"
+#include "dcc_scan.h"
 #include "radix_sort.h"
 
 #define CK(expr)                                           \
@@ -58,15 +58,8 @@ __global__ __launch_bounds__(SH_B) void k_sh_count(const uint32_t* off, const ui
   const uint64_t t = (uint64_t)blockIdx.x * SH_B + threadIdx.x;
   const uint32_t c = t < n ? sh_count(off, keys, nnz, t, rank, R) : 0u;
   if (t < n) cnt[t] = c;
-  uint32_t v = c;
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t b = 0;
-    for (uint32_t w = 0; w < SH_B / 64; w++) b += s_w[w];
-    bsum[blockIdx.x] = b;
-  }
+  const uint32_t b = dcc::block_reduce<SH_B / 64, dcc::AddOp<uint32_t>>(c, s_w);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = b;
 }
 
 __global__ __launch_bounds__(SH_B) void k_sh_scatter(const uint32_t* off, const uint64_t* keys,
@@ -76,18 +69,10 @@ __global__ __launch_bounds__(SH_B) void k_sh_scatter(const uint32_t* off, const 
                                                      uint32_t* off_out, uint64_t* keys_out,
                                                      uint8_t* at_out, uint32_t* src_out) {
   __shared__ uint32_t s_w[SH_B / 64];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint64_t t = (uint64_t)blockIdx.x * SH_B + threadIdx.x;
   const uint32_t c = t < n ? cnt[t] : 0u;
-  uint32_t x = c;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s_w[wv] = x;
-  __syncthreads();
-  uint32_t o = bsum[blockIdx.x] + x - c;
-  for (uint32_t w = 0; w < wv; w++) o += s_w[w];
+  uint32_t tot;
+  uint32_t o = bsum[blockIdx.x] + dcc::block_excl<SH_B / 64, dcc::AddOp<uint32_t>>(c, s_w, tot);
   if (t < n) {
     off_out[t] = o;
     const uint64_t s = min((uint64_t)off[t], nnz), e = min((uint64_t)off[t + 1], nnz);
