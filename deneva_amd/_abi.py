@@ -28,6 +28,7 @@ RD, WR, XP, SCAN = 0, 1, 2, 3  # access_t, system/global.h:287
 RC_RCOK, RC_ABORT, RC_WAIT = 0, 2, 3  # RC, system/global.h:236
 KEY_RESERVED = 0xFFFFFFFFFFFFFFFF
 GROUP_NONE = 0xFFFFFFFF
+ACCESS_NONE = 0xFFFFFFFF
 DEVICE_PTRS = 0x1
 OCC_APPEND_HISTORY = 0x2
 OCC_DEFER_FINISH = 0x8
@@ -229,6 +230,9 @@ _SIGS = [
     ("dcc_index_last_ms", C.c_double, [_P]),
     ("dcc_calvin_order_epoch_held", C.c_int,
      [_P, C.POINTER(Batch), C.POINTER(CalvinHeld), _P, _P, _P, C.POINTER(Stats)]),
+    ("dcc_nowait_lock_epoch", C.c_int,
+     [_P, C.POINTER(Batch), C.POINTER(CalvinHeld), _P, _P, C.POINTER(Stats)]),
+    ("dcc_nowait_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
     ("dcc_ycsb_params_default", None, [C.POINTER(YcsbParams)]),
     ("dcc_gen_ycsb", C.c_int, [C.POINTER(YcsbParams), _P, _P, _P, _P]),
     ("dcc_tpcc_params_default", None, [C.POINTER(TpccParams)]),

@@ -199,6 +199,9 @@ struct dcc_ctx {
   uint32_t mt_tag = 0;   // its round tag (monotone; the buffer is zeroed when it wraps)
   // GPU index (index.hip): key table, newest insert ordinal per key, rows
   DevBuf ix_keys, ix_ord, ix_rows, ix_cnt, wv_buf, ix_scr, wv_hbuf, wv_obuf;
+  // NO_WAIT lock epoch (nowait.hip): counters, slot id per request, undecided
+  // lists (ping-pong), conflict ordinals and held rows of a host call
+  DevBuf nw_misc, nw_sid, nw_list, nw_conf, nw_hk, nw_ha;
   uint32_t ix_bits = 0;
   uint64_t ix_nkeys = 0, ix_nrows = 0;
   double ix_last_ms = 0;
@@ -329,6 +332,10 @@ struct dcc_ctx {
                      bool* full);
   int calvin_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint32_t* out_group,
                    uint8_t* out_rc, uint32_t* out_wave, dcc_stats* st);
+  // NO_WAIT 2PL (nowait.hip)
+  int nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
+  int nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
+                   uint32_t* out_conflict, dcc_stats* st);
   // device-side key-shard partition (shard_dev.hip): rank `rank` of R of a
   // multi-GPU context; sb is the shard as a device batch
   DevBuf sh_off, sh_keys, sh_at, sh_src, sh_cnt, sh_bsum, sh_rc, sh_tn, sh_grp;

@@ -1,0 +1,571 @@
+// NO_WAIT two-phase locking for a whole epoch (dcc_nowait_lock_epoch).
+//
+// Reference: the txns of the batch call get_row for their accesses, txn by
+// txn in index order, against Row_lock in NO_WAIT mode (storage/row.cpp:
+// 226-238, concurrency_control/row_lock.cpp:52-216).  An aborted txn releases
+// what it took (system/txn.cpp:747-761, row_lock.cpp:240-256) and leaves no
+// trace, a txn that gets every lock holds them to the end of the epoch, so
+//
+//   abort(i) <=> self_conflict(i)
+//             OR some access (k, t) of i conflicts with the held prefix
+//             OR exists j < i, commit(j), j holds k in mode t', t == EX or t' == EX
+//
+// Per key this needs two minima over the non-aborted requesters: of any mode
+// (Slot::own) and of EX mode (Slot::aux).  An EX access of txn i is KILLED if
+// the `own` minimum is a committed txn below i and BLOCKED if it is an
+// undecided one; an SH access reads `aux` the same way.  The lowest undecided
+// txn is decided in every round, so the rounds reach the unique fixed point.
+//
+// Words are the tagged owner words of dcc_device.h with the txn index shifted
+// by one: tag 0 | 0 is a held row (below every txn), tag 0 | i + 1 a committed
+// requester, round tag | i + 1 an undecided requester of that round.  Newer
+// rounds carry smaller tags, so one atomicMin replaces the stale words of
+// older rounds, and a committed word is never displaced.
+//
+// A txn takes P consecutive lanes (P = the power of two >= the epoch's
+// longest txn), one access per lane, so adjacent lanes load adjacent
+// accesses; per-txn reductions are ballots masked to the txn's lanes.
+//
+// Kernels:  k_nw_check   offsets / reserved keys / longest txn
+//           k_nw_held    held rows into the table (tag-0 words)
+//           k_nw_build   every requested key into the table, the slot id of
+//                        every request, self-conflicts decided, round-1 words
+//           k_nw_decide  one round over the undecided list: KILLED -> abort,
+//                        clear -> commit + tag-0 words, BLOCKED -> next list
+//           k_nw_publish the next round's words of the txns still undecided
+//           k_nw_retag   round tags exhausted: drop every tagged word
+//           k_nw_final   RC bytes, counts, first conflicting request
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+
+#include "dcc.h"
+#include "dcc_ctx.h"
+#include "dcc_device.h"
+#include "occ_kernels.h"
+
+using namespace dcc;
+
+#define CK(expr)                                           \
+  do {                                                     \
+    hipError_t e_ = (expr);                                \
+    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
+  } while (0)
+#define CR(expr)                 \
+  do {                           \
+    int r_ = (expr);             \
+    if (r_ != DCC_OK) return r_; \
+  } while (0)
+
+namespace {
+
+constexpr uint32_t NW_T = 256;        // threads per workgroup
+constexpr uint32_t NW_RING = 64;      // list-length ring (> the rounds of one host batch)
+constexpr uint32_t NW_STAGE = 1024;   // blocked txns a workgroup stages before one list append
+constexpr uint32_t NW_ERR_OFF = 1, NW_ERR_KEY = 2, NW_ERR_FULL = 4, NW_ERR_STATE = 8;
+// counter words (nw_misc)
+constexpr uint32_t NW_C_ERR = 0, NW_C_MAXLEN = 1, NW_C_NEX = 2, NW_C_RO = 3, NW_C_COMMIT = 4,
+                   NW_C_RING = 8, NW_C_WORDS = NW_C_RING + NW_RING;
+
+__device__ inline uint32_t is_ex(uint8_t t) { return (t == DCC_RD || t == DCC_SCAN) ? 0u : 1u; }
+
+// The P = 2^lp lanes of a txn inside the wave.
+struct Seg {
+  uint32_t a;     // access ordinal of this lane
+  uint32_t gl;    // txn of this lane within the workgroup's step
+  uint32_t seg0;  // first lane of the txn
+  uint64_t mask;  // the txn's lanes
+};
+__device__ inline Seg seg_of(uint32_t lp) {
+  const uint32_t P = 1u << lp;
+  Seg s;
+  s.a = threadIdx.x & (P - 1);
+  s.gl = threadIdx.x >> lp;
+  s.seg0 = lane_id() & ~(P - 1);
+  s.mask = (P == 64 ? ~0ull : ((1ull << P) - 1ull)) << s.seg0;
+  return s;
+}
+
+// A txn names a row twice with EX on either side (NO_WAIT keeps no owner
+// list, row_lock.cpp:176-182): the lanes of the later requests.  Rows compare
+// by slot id (one slot per key).  Every lane of the wave calls it.
+__device__ inline bool self_conflict(const Seg& g, uint32_t lp, bool v, uint32_t s, uint32_t ex) {
+  bool sc = false;
+  const uint32_t P = 1u << lp;
+  for (uint32_t q = 0; q + 1 < P; q++) {
+    if (!ballot64(v && g.a > q)) break;  // no lane of the wave has an earlier access q
+    const uint32_t so = __shfl(s, (int)(g.seg0 + q));
+    const uint32_t eo = __shfl(ex, (int)(g.seg0 + q));
+    if (v && q < g.a && so == s && s != SID_NONE && (ex | eo)) sc = true;
+  }
+  return sc;
+}
+
+__global__ __launch_bounds__(NW_T) void k_nw_check(const uint32_t* __restrict__ off, uint64_t n,
+                                                   const uint64_t* __restrict__ keys, uint64_t nnz,
+                                                   uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t s_len, s_err;
+  if (threadIdx.x == 0) {
+    s_len = 0;
+    s_err = 0;
+  }
+  __syncthreads();
+  uint32_t len = 0, err = 0;
+  const uint64_t tid = (uint64_t)blockIdx.x * NW_T + threadIdx.x, stride = (uint64_t)gridDim.x * NW_T;
+  for (uint64_t t = tid; t < n; t += stride) {
+    const uint32_t a0 = off[t], b0 = off[t + 1];
+    if (b0 < a0) err |= NW_ERR_OFF;
+    else len = max(len, b0 - a0);
+    if (t == 0 && a0 != 0) err |= NW_ERR_OFF;
+    if (t == n - 1 && b0 != nnz) err |= NW_ERR_OFF;
+  }
+  for (uint64_t x = tid; x < nnz; x += stride)
+    if (keys[x] == KEY_EMPTY) err |= NW_ERR_KEY;
+  if (len) atomicMax(&s_len, len);
+  if (err) atomicOr(&s_err, err);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_len) atomicMax(&cnt[NW_C_MAXLEN], s_len);
+    if (s_err) atomicOr(&cnt[NW_C_ERR], s_err);
+  }
+}
+
+__global__ __launch_bounds__(NW_T) void k_nw_held(const uint64_t* __restrict__ keys,
+                                                  const uint8_t* __restrict__ at, uint64_t n, Slot* tab,
+                                                  uint32_t mask, uint32_t* __restrict__ cnt) {
+  const uint64_t stride = (uint64_t)gridDim.x * NW_T;
+  for (uint64_t x = (uint64_t)blockIdx.x * NW_T + threadIdx.x; x < n; x += stride) {
+    const uint64_t key = keys[x];
+    if (key == KEY_EMPTY) {
+      atomicOr(&cnt[NW_C_ERR], NW_ERR_KEY);
+      continue;
+    }
+    const uint32_t s = table_insert(tab, mask, key);
+    if (s == SID_NONE) {
+      atomicOr(&cnt[NW_C_ERR], NW_ERR_FULL);
+      continue;
+    }
+    own_min(&tab[s].own, 0u);  // committed word below every txn
+    if (is_ex(at[x])) own_min(&tab[s].aux, 0u);
+  }
+}
+
+struct NwArgs {
+  uint64_t n;
+  const uint32_t* off;
+  const uint64_t* keys;
+  const uint8_t* at;
+  Slot* tab;
+  uint32_t mask;
+  uint32_t lp;  // log2 lanes per txn
+  uint32_t* sid;
+  uint8_t* state;
+  uint32_t* cnt;
+};
+
+__global__ __launch_bounds__(NW_T) void k_nw_build(NwArgs A) {
+  __shared__ uint32_t s_ro, s_nex;
+  if (threadIdx.x == 0) {
+    s_ro = 0;
+    s_nex = 0;
+  }
+  __syncthreads();
+  const Seg g = seg_of(A.lp);
+  const uint32_t gpb = NW_T >> A.lp;
+  uint32_t ro = 0, nex = 0;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
+    const uint64_t t = g0 + g.gl;
+    const bool tv = t < A.n;
+    uint32_t o0 = 0, len = 0;
+    if (tv) {
+      o0 = A.off[t];
+      len = A.off[t + 1] - o0;
+    }
+    const bool v = tv && g.a < len;
+    const uint64_t x = (uint64_t)o0 + g.a;
+    uint32_t ex = 0, s = SID_NONE;
+    if (v) {
+      ex = is_ex(A.at[x]);
+      s = table_insert(A.tab, A.mask, A.keys[x]);
+      A.sid[x] = s;
+      if (s == SID_NONE) atomicOr(&A.cnt[NW_C_ERR], NW_ERR_FULL);
+    }
+    const bool sc = self_conflict(g, A.lp, v, s, ex);
+    const bool selfc = (ballot64(sc) & g.mask) != 0;
+    const uint64_t exb = ballot64(v && ex) & g.mask;
+    if (v && !selfc && s != SID_NONE) {
+      const uint32_t w = own_word(round_tag(1), (uint32_t)t + 1u);
+      own_min(&A.tab[s].own, w);
+      if (ex) own_min(&A.tab[s].aux, w);
+    }
+    if (tv && g.a == 0) {
+      A.state[t] = selfc ? ST_ABORT : ST_UNDECIDED;  // an aborted txn publishes nothing
+      ro += exb ? 0u : 1u;
+      nex += (uint32_t)__popcll(exb);
+    }
+  }
+  if (ro) atomicAdd(&s_ro, ro);
+  if (nex) atomicAdd(&s_nex, nex);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_ro) atomicAdd(&A.cnt[NW_C_RO], s_ro);
+    if (s_nex) atomicAdd(&A.cnt[NW_C_NEX], s_nex);
+  }
+}
+
+// One round.  list == nullptr: every txn (round 1), else the *m_in txns of
+// the list.  Blocked txns are staged in LDS and appended to list_out with one
+// atomic per NW_STAGE of them (the list order is free: decisions do not
+// depend on it).  A commit publishes its tag-0 words right away: a reader
+// that sees one early is killed by a txn that does kill it.
+__global__ __launch_bounds__(NW_T) void k_nw_decide(NwArgs A, uint32_t tag, const uint32_t* __restrict__ list,
+                                                    const uint32_t* __restrict__ m_in,
+                                                    uint32_t* __restrict__ list_out, uint32_t* m_out) {
+  __shared__ uint32_t l_buf[NW_STAGE];
+  __shared__ uint32_t l_cnt, l_base;
+  if (threadIdx.x == 0) l_cnt = 0;
+  __syncthreads();
+  const Seg g = seg_of(A.lp);
+  const uint32_t gpb = NW_T >> A.lp;
+  const uint64_t m = list ? (uint64_t)*m_in : A.n;
+  auto flush = [&]() {  // every thread of the workgroup
+    const uint32_t c = l_cnt;
+    if (threadIdx.x == 0 && c) l_base = atomicAdd(m_out, c);
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < c; q += NW_T) list_out[l_base + q] = l_buf[q];
+    __syncthreads();
+    if (threadIdx.x == 0) l_cnt = 0;
+    __syncthreads();
+  };
+  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < m; g0 += (uint64_t)gridDim.x * gpb) {
+    const uint64_t e = g0 + g.gl;
+    const bool ev = e < m;
+    uint32_t t = 0;
+    bool act = false;
+    if (ev) {
+      t = list ? list[e] : (uint32_t)e;
+      act = A.state[t] == ST_UNDECIDED;
+    }
+    uint32_t o0 = 0, len = 0;
+    if (act) {
+      o0 = A.off[t];
+      len = A.off[t + 1] - o0;
+    }
+    const bool v = act && g.a < len;
+    const uint64_t x = (uint64_t)o0 + g.a;
+    uint32_t ex = 0, s = SID_NONE, ps = 0;
+    if (v) {
+      ex = is_ex(A.at[x]);
+      s = A.sid[x];
+      if (s != SID_NONE) ps = own_status(ex ? A.tab[s].own : A.tab[s].aux, tag, t + 1u);
+    }
+    const bool killed = (ballot64(ps & PS_KILLED) & g.mask) != 0;
+    const bool blocked = !killed && (ballot64(ps & PS_BLOCKED) & g.mask) != 0;
+    if (v && !killed && !blocked && s != SID_NONE) {  // commit: hold every lock to the end of the epoch
+      own_min(&A.tab[s].own, t + 1u);
+      if (ex) own_min(&A.tab[s].aux, t + 1u);
+    }
+    const bool lead = act && g.a == 0;
+    if (lead && !blocked) A.state[t] = killed ? ST_ABORT : ST_COMMIT;
+    const bool app = lead && blocked;
+    const uint64_t bm = ballot64(app);
+    if (bm) {
+      uint32_t base = 0;
+      if (lane_id() == 0) base = atomicAdd(&l_cnt, (uint32_t)__popcll(bm));
+      base = __shfl(base, 0);
+      if (app) l_buf[base + (uint32_t)__popcll(bm & lanemask_lt())] = t;
+    }
+    __syncthreads();
+    const uint32_t staged = l_cnt;
+    __syncthreads();  // every thread has read the count before the next step adds to it
+    if (staged > NW_STAGE - NW_T) flush();  // the next step adds at most NW_T
+  }
+  flush();
+}
+
+// The words of round `tag` for the txns still undecided (the list of the
+// round before).  Workgroup 0 clears the length word that round appends to.
+__global__ __launch_bounds__(NW_T) void k_nw_publish(NwArgs A, uint32_t tag, const uint32_t* __restrict__ list,
+                                                     const uint32_t* __restrict__ m_in, uint32_t* m_zero) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *m_zero = 0;
+  const Seg g = seg_of(A.lp);
+  const uint32_t gpb = NW_T >> A.lp;
+  const uint64_t m = *m_in;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < m; g0 += (uint64_t)gridDim.x * gpb) {
+    const uint64_t e = g0 + g.gl;
+    if (e >= m) continue;
+    const uint32_t t = list[e];
+    const uint32_t o0 = A.off[t], len = A.off[t + 1] - o0;
+    if (g.a >= len) continue;
+    const uint64_t x = (uint64_t)o0 + g.a;
+    const uint32_t s = A.sid[x];
+    if (s == SID_NONE) continue;
+    const uint32_t w = own_word(tag, t + 1u);
+    own_min(&A.tab[s].own, w);
+    if (is_ex(A.at[x])) own_min(&A.tab[s].aux, w);
+  }
+}
+
+__global__ __launch_bounds__(NW_T) void k_nw_retag(Slot* tab, uint64_t cap) {
+  const uint64_t stride = (uint64_t)gridDim.x * NW_T;
+  for (uint64_t h = (uint64_t)blockIdx.x * NW_T + threadIdx.x; h < cap; h += stride) {
+    if (tab[h].key == KEY_EMPTY) continue;
+    if (tab[h].own >> IDX_BITS) tab[h].own = OWN_EMPTY;
+    if (tab[h].aux >> IDX_BITS) tab[h].aux = OWN_EMPTY;
+  }
+}
+
+// RC bytes and the commit count; for an aborted txn the first access whose
+// lock_get returned Abort: the first that names a row again with EX on either
+// side, or that conflicts with a held row or with a committed txn below it
+// (the committed-only words: tag 0).
+__global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict__ rc,
+                                                   uint32_t* __restrict__ conflict) {
+  __shared__ uint32_t s_commit;
+  if (threadIdx.x == 0) s_commit = 0;
+  __syncthreads();
+  const Seg g = seg_of(A.lp);
+  const uint32_t gpb = NW_T >> A.lp;
+  uint32_t commits = 0;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
+    const uint64_t t = g0 + g.gl;
+    const bool tv = t < A.n;
+    const uint8_t st = tv ? A.state[t] : (uint8_t)ST_COMMIT;
+    const bool ab = tv && st != ST_COMMIT;
+    if (tv && g.a == 0) {
+      rc[t] = st == ST_COMMIT ? DCC_RC_RCOK : DCC_RC_ABORT;
+      commits += st == ST_COMMIT ? 1u : 0u;
+      if (st == ST_UNDECIDED) atomicOr(&A.cnt[NW_C_ERR], NW_ERR_STATE);
+    }
+    if (!conflict) continue;
+    if (!ballot64(ab)) {  // no aborted txn in the wave
+      if (tv && g.a == 0) conflict[t] = DCC_ACCESS_NONE;
+      continue;
+    }
+    uint32_t o0 = 0, len = 0;
+    if (ab) {
+      o0 = A.off[t];
+      len = A.off[t + 1] - o0;
+    }
+    const bool v = ab && g.a < len;
+    const uint64_t x = (uint64_t)o0 + g.a;
+    uint32_t ex = 0, s = SID_NONE;
+    bool c = false;
+    if (v) {
+      ex = is_ex(A.at[x]);
+      s = A.sid[x];
+      if (s != SID_NONE) {
+        const uint32_t w = ex ? A.tab[s].own : A.tab[s].aux;
+        c = (w >> IDX_BITS) == 0 && (w & IDX_MASK) < (uint32_t)t + 1u;
+      }
+    }
+    c = self_conflict(g, A.lp, v, s, ex) || c;
+    const uint64_t cb = ballot64(c) & g.mask;
+    if (tv && g.a == 0) {
+      uint32_t o = DCC_ACCESS_NONE;
+      if (ab) {
+        if (cb) o = (uint32_t)__builtin_ctzll(cb) - g.seg0;
+        else atomicOr(&A.cnt[NW_C_ERR], NW_ERR_STATE);  // aborted without a conflicting request
+      }
+      conflict[t] = o;
+    }
+  }
+  if (commits) atomicAdd(&s_commit, commits);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_commit) atomicAdd(&A.cnt[NW_C_COMMIT], s_commit);
+}
+
+unsigned nw_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
+  const uint64_t b = (items + per_block - 1) / per_block;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, max_grid));
+}
+
+}  // namespace
+
+int dcc_ctx::nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict) {
+  CR(nw_misc.ensure(this, NW_C_WORDS * 4, "nowait counters"));
+  CR(nw_sid.ensure(this, std::max<uint64_t>(nnz, 1) * 4, "nowait slot ids"));
+  CR(nw_list.ensure(this, 2 * std::max<uint64_t>(n, 1) * 4, "nowait undecided lists"));
+  if (with_conflict) CR(nw_conf.ensure(this, std::max<uint64_t>(n, 1) * 4, "nowait conflicts"));
+  CR(state.ensure(this, n + 16, "state"));
+  CR(rc.ensure(this, n + 16, "rc"));
+  CR(table.ensure(this, table_capacity(nnz) * sizeof(Slot), "table"));
+  return DCC_OK;
+}
+
+int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
+                          uint32_t* out_conflict, dcc_stats* st) {
+  dcc_ctx* ctx = this;
+  const auto t_wall0 = std::chrono::steady_clock::now();
+  if (!out_rc) return fail(DCC_EINVAL, "nowait: null out_rc");
+  CR(check_batch(b, false));  // the offsets are checked on the device (k_nw_check)
+  if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "nowait: single-GPU engine");
+  const uint64_t hn = held ? held->n : 0;
+  if (hn && (!held->keys || !held->acctype)) return fail(DCC_EINVAL, "nowait: null held keys/acctype");
+  const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
+  dcc_stats S;
+  memset(&S, 0, sizeof S);
+  S.n_shards = 1;
+  if (b->n_txn == 0) {
+    if (st) *st = S;
+    return DCC_OK;
+  }
+  if (b->n_txn >= (uint64_t)IDX_MASK)  // owner words carry index + 1
+    return fail(DCC_ERANGE, "nowait: n_txn %llu exceeds %u", (unsigned long long)b->n_txn, IDX_MASK - 1);
+  DevBatch d;
+  CR(stage_batch(b, d));
+  const uint64_t n = d.n, m = d.nnz;
+  const uint64_t cap = table_capacity(m + hn);
+  if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
+  const uint32_t mask = (uint32_t)(cap - 1);
+  CR(nowait_reserve(n, m, out_conflict != nullptr && !dev));
+  CR(table.ensure(this, cap * sizeof(Slot), "table"));
+  uint32_t* cnt = (uint32_t*)nw_misc.p;
+  uint32_t* ring = cnt + NW_C_RING;
+  uint32_t* lists[2] = {(uint32_t*)nw_list.p, (uint32_t*)nw_list.p + n};
+  uint8_t* rc_dev = dev ? out_rc : (uint8_t*)rc.p;
+  uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)nw_conf.p) : nullptr;
+  const unsigned max_grid = (unsigned)n_cu * 16;
+
+  // reject a malformed batch before anything indexes with its offsets
+  CK(hipMemsetAsync(cnt, 0, NW_C_WORDS * 4, stream));
+  k_nw_check<<<nw_grid(std::max(n, m), NW_T * 4, max_grid), NW_T, 0, stream>>>(d.off, n, d.keys, m, cnt);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(hmisc, cnt, 8, hipMemcpyDeviceToHost, stream));
+  CK(hipStreamSynchronize(stream));
+  uint32_t maxlen = 0;
+  {
+    const uint32_t* hc = (const uint32_t*)hmisc;
+    if (hc[NW_C_ERR] & NW_ERR_OFF) return fail(DCC_EINVAL, "batch: malformed offsets");
+    if (hc[NW_C_ERR] & NW_ERR_KEY) return fail(DCC_EINVAL, "batch: key equal to DCC_KEY_RESERVED");
+    maxlen = hc[NW_C_MAXLEN];
+    if (maxlen > MAX_TXN_LEN)
+      return fail(DCC_EINVAL, "batch: a txn has %u accesses (> MAX_ROW_PER_TXN=%u)", maxlen, MAX_TXN_LEN);
+  }
+  uint32_t lp = 0;
+  while ((1u << lp) < maxlen) lp++;
+  const uint64_t per_block = NW_T >> lp;  // txns per workgroup step
+
+  const bool prof = profiling;
+  CK(hipEventRecord(ev0, stream));
+  if (prof) CK(hipEventRecord(pev[0], stream));
+  Slot* tab = (Slot*)table.p;
+  CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
+  if (hn) {
+    const uint64_t* hk = held->keys;
+    const uint8_t* ha = held->acctype;
+    if (!dev) {
+      CR(nw_hk.ensure(this, hn * 8, "nowait held keys"));
+      CR(nw_ha.ensure(this, hn, "nowait held access types"));
+      CK(hipMemcpyAsync(nw_hk.p, held->keys, hn * 8, hipMemcpyHostToDevice, stream));
+      CK(hipMemcpyAsync(nw_ha.p, held->acctype, hn, hipMemcpyHostToDevice, stream));
+      hk = (const uint64_t*)nw_hk.p;
+      ha = (const uint8_t*)nw_ha.p;
+    }
+    k_nw_held<<<nw_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt);
+  }
+  NwArgs A{n, d.off, d.keys, d.acctype, tab, mask, lp, (uint32_t*)nw_sid.p, (uint8_t*)state.p, cnt};
+  k_nw_build<<<nw_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
+  CK(hipGetLastError());
+  if (prof) CK(hipEventRecord(pev[1], stream));
+
+  // ---- rounds: decide(r) reads its list length from ring[r % NW_RING] and
+  // appends the blocked txns to ring[(r + 1) % NW_RING], which publish(r)
+  // cleared (the whole ring is clear before round 1).  Several rounds are
+  // enqueued between host synchronisations; rounds past the fixed point find
+  // empty lists.
+  uint32_t r = 1, rounds = 0;
+  uint64_t m_bound = n;
+  uint32_t batch = std::min<uint32_t>(2, batch_max);
+  bool done = false;
+  while (!done) {
+    const uint32_t r0 = r;
+    for (uint32_t q = 0; q < batch; q++, r++) {
+      const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;  // tags 62 .. 1, then again
+      const uint32_t tag = round_tag(er);
+      const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
+      const uint32_t* min_ = &ring[r % NW_RING];
+      const unsigned grid = nw_grid(m_bound, per_block, max_grid);
+      if (r > 1) {
+        if (er == 1)  // tag space exhausted: drop the tagged words, every undecided txn republishes
+          k_nw_retag<<<nw_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
+        k_nw_publish<<<grid, NW_T, 0, stream>>>(A, tag, lin, min_, &ring[(r + 1) % NW_RING]);
+      }
+      k_nw_decide<<<grid, NW_T, 0, stream>>>(A, tag, lin, min_, lists[(r + 1) & 1], &ring[(r + 1) % NW_RING]);
+      if (prof && r == 1) CK(hipEventRecord(pev[2], stream));
+    }
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(hmisc, ring, NW_RING * 4, hipMemcpyDeviceToHost, stream));
+    CK(hipStreamSynchronize(stream));
+    const uint32_t* hr = (const uint32_t*)hmisc;
+    for (uint32_t q = r0; q < r; q++) {
+      const uint32_t left = hr[(q + 1) % NW_RING];
+      if (left == 0) {
+        rounds = q;
+        done = true;
+        break;
+      }
+      m_bound = left;
+    }
+    if (!done && r > n + 2) return fail(DCC_EIO, "nowait: fixed point did not converge");
+    batch = std::min<uint32_t>(batch * 2, std::min<uint32_t>(batch_max, NW_RING / 2));
+  }
+  if (prof) CK(hipEventRecord(pev[3], stream));
+  k_nw_final<<<nw_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
+  CK(hipGetLastError());
+  if (prof) CK(hipEventRecord(pev[4], stream));
+  CK(hipEventRecord(ev1, stream));
+  if (!dev) {
+    CK(hipMemcpyAsync(out_rc, rc_dev, n, hipMemcpyDeviceToHost, stream));
+    if (out_conflict) CK(hipMemcpyAsync(out_conflict, conf_dev, n * 4, hipMemcpyDeviceToHost, stream));
+  }
+  CK(hipMemcpyAsync(hmisc, cnt, NW_C_RING * 4, hipMemcpyDeviceToHost, stream));
+  CK(hipStreamSynchronize(stream));
+  const uint32_t* hc = (const uint32_t*)hmisc;
+  if (hc[NW_C_ERR] & NW_ERR_KEY) return fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
+  if (hc[NW_C_ERR] & NW_ERR_FULL) return fail(DCC_EIO, "nowait: lock table full");
+  if (hc[NW_C_ERR] & NW_ERR_STATE) return fail(DCC_EIO, "nowait: inconsistent decisions");
+  float ms = 0;
+  CK(hipEventElapsedTime(&ms, ev0, ev1));
+  if (prof)
+    for (int q = 0; q < 4; q++) {
+      float pm = 0;
+      CK(hipEventElapsedTime(&pm, pev[q], pev[q + 1]));
+      S.phase_ms[q] = pm;
+    }
+  S.rounds = rounds;
+  S.n_commit = hc[NW_C_COMMIT];
+  S.n_abort = n - hc[NW_C_COMMIT];
+  S.nnz_w = hc[NW_C_NEX];
+  S.n_readonly = hc[NW_C_RO];
+  S.alg_bytes = dcc_nowait_alg_bytes(n, m, out_conflict != nullptr);
+  S.device_ms = ms;
+  S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0).count();
+  if (st) *st = S;
+  return DCC_OK;
+}
+
+extern "C" uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict) {
+  // offsets, key + access type per request, one 16-B lock-table slot per
+  // request, RC byte, conflict ordinal
+  return 4 * (n_txn + 1) + 9 * nnz + 16 * nnz + n_txn + (with_conflict ? 4 * n_txn : 0);
+}
+
+extern "C" int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const dcc_calvin_held* held,
+                                     uint8_t* out_rc, uint32_t* out_conflict, dcc_stats* out_stats) {
+  if (!ctx || !batch || !out_rc) return DCC_EINVAL;
+  dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
+  if (ctx->multi) {     // the whole epoch on rank 0 (the lock table is one GPU's)
+    dcc_ctx* s = dcc_multi_rank0(ctx);
+    dcc_comm_state* const cm = s->comm;  // one GPU's engine: no collective
+    s->comm = nullptr;
+    const int e = s->nowait_epoch(batch, held, out_rc, out_conflict, out_stats);
+    s->comm = cm;
+    if (e != DCC_OK) ctx->last_error = s->last_error;
+    return e;
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
+  return ctx->nowait_epoch(batch, held, out_rc, out_conflict, out_stats);
+}

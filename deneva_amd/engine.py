@@ -449,6 +449,45 @@ class Engine:
         return (grp[:nnz] if want_group else None, rc[:n],
                 (wav[:n] if want_wave else None), st.as_dict())
 
+    # ------------------------------------------------------ NO_WAIT (2PL)
+    def nowait_lock_epoch(self, batch: EpochBatch, held=None, want_conflict: bool = True,
+                          out_rc=None, out_conflict=None):
+        """NO_WAIT lock acquisition of an epoch (dcc_nowait_lock_epoch): returns
+        (rc u8[n], conflict u32[n] | None, stats).  held = (keys u64[h],
+        acctype u8[h]): rows still locked by txns of earlier epochs.
+        conflict[i] is the ordinal of the request an aborted txn aborted at,
+        ACCESS_NONE for a committed one."""
+        n = batch.n_txn
+        dev = batch.on_device
+        if dev:
+            import torch
+            d = batch.offsets.device
+            if out_rc is None:
+                out_rc = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
+            if want_conflict and out_conflict is None:
+                out_conflict = torch.empty(max(n, 1), dtype=torch.int32, device=d)
+        else:
+            if out_rc is None:
+                out_rc = np.empty(max(n, 1), np.uint8)
+            if want_conflict and out_conflict is None:
+                out_conflict = np.empty(max(n, 1), np.uint32)
+        if not want_conflict:
+            out_conflict = None
+        if out_rc.shape[0] < n or (out_conflict is not None and out_conflict.shape[0] < n):
+            raise ValueError("nowait_lock_epoch: output buffer shorter than the epoch")
+        st = _abi.Stats()
+        b = batch.to_c()
+        h = None
+        if held is not None:
+            hk, ha = held
+            if not dev:
+                hk = np.ascontiguousarray(hk, np.uint64)
+                ha = np.ascontiguousarray(ha, np.uint8)
+            h = C.byref(_abi.CalvinHeld(int(hk.shape[0]), _ptr(hk), _ptr(ha)))
+        _check(lib.dcc_nowait_lock_epoch(self._h, C.byref(b), h, _ptr(out_rc), _ptr(out_conflict),
+                                         C.byref(st)), self._h)
+        return out_rc[:n], (out_conflict[:n] if want_conflict else None), st.as_dict()
+
     def calvin_dispatch(self, wave, order=None):
         """Wave dispatch lists (dcc_calvin_dispatch): returns (wave_off u32[W+1],
         txn u32[n]) — txn[wave_off[w]:wave_off[w+1]] run in wave w."""
@@ -584,6 +623,10 @@ def alg_bytes(n_txn: int, nnz: int, nnz_w: int) -> int:
 
 def calvin_alg_bytes(n_txn: int, nnz: int, with_order: bool, with_wave: bool) -> int:
     return int(lib.dcc_calvin_alg_bytes(n_txn, nnz, int(with_order), int(with_wave)))
+
+
+def nowait_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
+    return int(lib.dcc_nowait_alg_bytes(n_txn, nnz, int(with_conflict)))
 
 
 # ---------------------------------------------------------------- producers

@@ -438,6 +438,45 @@ int dcc_calvin_order_epoch_held(dcc_ctx* ctx, const dcc_batch* batch, const dcc_
                                 uint32_t* out_group, uint8_t* out_rc, uint32_t* out_wave,
                                 dcc_stats* out_stats);
 
+/* ------------------------------------------------------- NO_WAIT (2PL) */
+/* Epoch lock acquisition under CC_ALG NO_WAIT: the result equals the txns of
+ * the batch calling get_row for their accesses, txn by txn in index order and
+ * access by access in list order, against a Row_lock table in NO_WAIT mode
+ * (storage/row.cpp:226-238, concurrency_control/row_lock.cpp:52-216):
+ * RD/SCAN request LOCK_SH, everything else LOCK_EX (row.cpp:228); a request
+ * conflicts iff the row's lock_type is not LOCK_NONE and either side is EX
+ * (conflict_lock, row_lock.cpp:374-381); the first conflicting request aborts
+ * the txn (row_lock.cpp:86-90), which releases what it took (cleanup ->
+ * lock_release, system/txn.cpp:747-761, row_lock.cpp:240-256) and requests
+ * nothing more; a txn that gets every lock holds them all to the end of the
+ * epoch (strict 2PL).  NO_WAIT keeps no owner list (row_lock.cpp:176-182), so
+ * a txn naming a row twice with EX on either side aborts on its own second
+ * request; two SH requests on one row are fine.
+ *   held            rows still locked by txns of earlier epochs, (key, access
+ *                   type) pairs: EX-held if any entry of the row is EX, else
+ *                   SH-held; they enter the table before txn 0 and are never
+ *                   released.  May be NULL.
+ *   out_rc[i]       = DCC_RC_RCOK (holds every lock) or DCC_RC_ABORT
+ *   out_conflict[i] = for an aborted txn the ordinal within the txn (0-based
+ *                     from offsets[i]) of the first access whose lock_get
+ *                     returned Abort (the request txn.cpp:803-816 aborts at);
+ *                     DCC_ACCESS_NONE for a committed txn.  May be NULL.
+ * start_tn / finish_tn / order of the batch are ignored.  With DCC_DEVICE_PTRS
+ * the batch, the held arrays and the outputs are device memory.  The lock
+ * table lives for the call only: the caller carries held rows from one epoch
+ * to the next.  One GPU: a dcc_init_multi context runs the epoch on rank 0; a
+ * communicator of more than one rank is DCC_ENOTSUP.
+ * Stats: n_commit, n_abort, nnz_w (EX requests), n_readonly (txns with no EX
+ * request), rounds, device_ms, total_ms, alg_bytes (dcc_nowait_alg_bytes);
+ * with profiling phase_ms: 0 = table build, 1 = round 1, 2 = rounds >= 2,
+ * 3 = RC / conflict pass. */
+#define DCC_ACCESS_NONE 0xFFFFFFFFu
+int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const dcc_calvin_held* held,
+                          uint8_t* out_rc, uint32_t* out_conflict, dcc_stats* out_stats);
+/* Algorithmic bytes of one NO_WAIT epoch: 4(N+1) offsets + 9 nnz (key, type)
+ * + 16 nnz (one lock-table slot per request) + N (RC) [+ 4N conflict]. */
+uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
+
 /* Wave dispatch: the wave levels of an epoch
  * (out_wave of dcc_calvin_order_epoch) as the lists a dispatcher releases:
  * out_txn[out_wave_off[w] .. out_wave_off[w+1]) = the txns of wave w in

@@ -1,0 +1,116 @@
+"""Times the NO_WAIT lock epoch (dcc_nowait_lock_epoch) on resident device
+batches next to the OCC round solver (dcc_occ_validate_epoch with
+DCC_OPT_SOLVER = 1, the design it parallels), in one process on the same
+batches: the C2 shape (65,536 x 16, theta 0.9) and the headline shape
+(1,048,576 x 16, theta 0.9).
+
+    python tools/nowait_bench.py [--warmup 5] [--steps 20] [--shape both|c2|headline]
+                                 [--check-1m] [--json PATH]
+
+device_ms is the engine's own device time of the decision (HIP events on its
+stream around the kernels of one call, batch resident); the table reports the
+median of the timed calls with the minimum and maximum, the rounds, and
+alg_bytes / device_ms.  Parity with the Row_lock replay (tests/nowait_ref.py)
+is checked on the C2 shape after timing; --check-1m also replays the headline
+shape (~30 s of Python).  Phase times come from a separate profiled call."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import deneva_amd as d  # noqa: E402
+from deneva_amd import _abi  # noqa: E402
+from nowait_ref import replay  # noqa: E402  (checker only)
+
+
+def summary(stats):
+    ms = [s["device_ms"] for s in stats]
+    med = statistics.median(ms)
+    return {"device_ms": med, "device_ms_min": min(ms), "device_ms_max": max(ms),
+            "rounds": stats[-1]["rounds"], "alg_bytes": stats[-1]["alg_bytes"],
+            "alg_GBps": stats[-1]["alg_bytes"] / (med * 1e-3) / 1e9,
+            "n_commit": stats[-1]["n_commit"], "n_abort": stats[-1]["n_abort"]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--shape", choices=("both", "c2", "headline"), default="both",
+                    help="one shape only (for a kernel trace of that shape)")
+    ap.add_argument("--check-1m", action="store_true")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "nowait_bench needs cuda:0"
+    out = {}
+    with d.Engine(0) as eng:
+        for name, n in (("C2 65,536 x 16", 65536), ("headline 1,048,576 x 16", 1 << 20)):
+            if a.shape != "both" and (a.shape == "c2") != (n == 65536):
+                continue
+            b = d.gen_ycsb(n_txn=n, zipf_theta=0.9)
+            db = b.to_torch("cuda:0")
+            rc = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+            cf = torch.empty(n, dtype=torch.int32, device="cuda:0")
+            orc = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+            eng.reserve(b.n_txn, b.nnz)
+
+            def nowait():
+                return eng.nowait_lock_epoch(db, out_rc=rc, out_conflict=cf)[2]
+
+            def occ():
+                return eng.occ_validate_epoch(db, out_rc=orc)[2]
+
+            eng.set_option(_abi.OPT_SOLVER, 1)
+            res = {}
+            for _ in range(a.warmup):
+                nowait()
+                occ()
+            # alternate the two so that both see the same machine state
+            st_n, st_o = [], []
+            for _ in range(a.steps):
+                st_n.append(nowait())
+                st_o.append(occ())
+            torch.cuda.synchronize()
+            res["nowait"] = summary(st_n)
+            res["occ_rounds"] = summary(st_o)
+            res["ratio"] = res["nowait"]["device_ms"] / res["occ_rounds"]["device_ms"]
+            eng.set_profiling(True)
+            for key, fn in (("nowait", nowait), ("occ_rounds", occ)):
+                ph = [fn()["phase_ms"] for _ in range(5)]
+                res[key]["phase_ms"] = [statistics.median(p[q] for p in ph) for q in range(4)]
+            eng.set_profiling(False)
+            eng.set_option(_abi.OPT_SOLVER, 0)
+            if n == 65536 or a.check_1m:
+                erc, ecf = replay(b)
+                nowait()
+                res["parity_vs_replay"] = bool(
+                    np.array_equal(rc.cpu().numpy(), erc)
+                    and np.array_equal(cf.cpu().numpy().view(np.uint32), ecf))
+            out[name] = res
+            print(f"{name}:")
+            for key in ("nowait", "occ_rounds"):
+                r = res[key]
+                print(f"  {key:10s} device_ms {r['device_ms']:.3f} (min {r['device_ms_min']:.3f}, "
+                      f"max {r['device_ms_max']:.3f})  rounds {r['rounds']}  "
+                      f"alg {r['alg_GBps']:.1f} GB/s  commits {r['n_commit']}  "
+                      f"phase_ms {[round(x, 3) for x in r['phase_ms']]}")
+            print(f"  NO_WAIT / OCC rounds = {res['ratio']:.2f}"
+                  + (f"  parity_vs_replay {res['parity_vs_replay']}" if "parity_vs_replay" in res else ""))
+    print(json.dumps(out))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+    assert all(r.get("parity_vs_replay", True) for r in out.values()), "NO_WAIT differs from the replay"
+
+
+if __name__ == "__main__":
+    main()
