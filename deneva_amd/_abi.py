@@ -83,6 +83,23 @@ class CalvinHeld(C.Structure):
     _fields_ = [("n", C.c_uint64), ("keys", C.c_void_p), ("acctype", C.c_void_p)]
 
 
+class SelectOut(C.Structure):
+    """dcc_select_out: where dcc_batch_select writes the selection."""
+    _fields_ = [
+        ("cap_txn", C.c_uint64),
+        ("cap_nnz", C.c_uint64),
+        ("txn_base", C.c_uint64),
+        ("nnz_base", C.c_uint64),
+        ("offsets", C.c_void_p),
+        ("keys", C.c_void_p),
+        ("acctype", C.c_void_p),
+        ("start_tn", C.c_void_p),
+        ("finish_tn", C.c_void_p),
+        ("order", C.c_void_p),
+        ("src", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("rounds", C.c_uint32),
@@ -233,6 +250,10 @@ _SIGS = [
     ("dcc_nowait_lock_epoch", C.c_int,
      [_P, C.POINTER(Batch), C.POINTER(CalvinHeld), _P, _P, C.POINTER(Stats)]),
     ("dcc_nowait_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
+    ("dcc_batch_select", C.c_int,
+     [_P, C.POINTER(Batch), _P, C.c_uint8, _P, C.POINTER(SelectOut), C.POINTER(C.c_uint64),
+      C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    ("dcc_select_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]),
     ("dcc_ycsb_params_default", None, [C.POINTER(YcsbParams)]),
     ("dcc_gen_ycsb", C.c_int, [C.POINTER(YcsbParams), _P, _P, _P, _P]),
     ("dcc_tpcc_params_default", None, [C.POINTER(TpccParams)]),

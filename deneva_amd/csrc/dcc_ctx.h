@@ -202,6 +202,9 @@ struct dcc_ctx {
   // NO_WAIT lock epoch (nowait.hip): counters, slot id per request, undecided
   // lists (ping-pong), conflict ordinals and held rows of a host call
   DevBuf nw_misc, nw_sid, nw_list, nw_conf, nw_hk, nw_ha;
+  // select by decision (select.hip): control words, tile pairs; rc / src_in
+  // and the output arrays of a host call
+  DevBuf sel_misc, sel_part, sel_in, sel_out;
   uint32_t ix_bits = 0;
   uint64_t ix_nkeys = 0, ix_nrows = 0;
   double ix_last_ms = 0;
@@ -336,6 +339,10 @@ struct dcc_ctx {
   int nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
   int nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
                    uint32_t* out_conflict, dcc_stats* st);
+  // select by decision into a CSR (select.hip)
+  int select_reserve(uint64_t n, uint64_t nnz);
+  int select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want, const uint32_t* src_in,
+                   const dcc_select_out* out, uint64_t* out_n, uint64_t* out_nnz, dcc_stats* st);
   // device-side key-shard partition (shard_dev.hip): rank `rank` of R of a
   // multi-GPU context; sb is the shard as a device batch
   DevBuf sh_off, sh_keys, sh_at, sh_src, sh_cnt, sh_bsum, sh_rc, sh_tn, sh_grp;

@@ -281,6 +281,7 @@ std::vector<DevBuf*> dcc_ctx::all_bufs() {
                             &mt_misc, &mt_slot, &mt_sval, &mt_slot2, &mt_sval2, &mt_sfl,
                             &mt_stx, &mt_txn, &mt_agg, &mt_sflB, &mt_stxB, &mt_k1, &mt_tcnt, &mt_ul, &mt_lb, &mt_ptab, &ix_keys, &ix_ord, &ix_rows, &ix_cnt, &wv_buf, &ix_scr, &wv_hbuf, &wv_obuf,
                             &nw_misc, &nw_sid, &nw_list, &nw_conf, &nw_hk, &nw_ha,
+                            &sel_misc, &sel_part, &sel_in, &sel_out,
                             &h_K[0], &h_K[1], &h_V[0], &h_V[1], &h_scr, &h_bsum, &h_bm,
                             &nar_keys, &nar_at, &nar_tn, &fin_ctl, &fdyn, &fin_off, &fin_keys, &fin_at, &fin_state, &fin_hasw, &fin_rc, &fin_cnt,
                             &sh_off, &sh_keys, &sh_at, &sh_src, &sh_cnt, &sh_bsum, &sh_rc, &sh_tn, &sh_grp};
@@ -309,6 +310,7 @@ extern "C" int dcc_reserve(dcc_ctx* ctx, uint64_t max_txn, uint64_t max_nnz) {
   if (!rc) rc = ctx->hasw.ensure(ctx, max_txn + 16, "hasw");
   if (!rc) rc = ctx->rc.ensure(ctx, max_txn + 16, "rc");
   if (!rc) rc = ctx->nowait_reserve(max_txn, max_nnz, true);
+  if (!rc) rc = ctx->select_reserve(max_txn, max_nnz);
   if (rc) return rc;
   return ctx->reserve_occ(max_txn, max_nnz, max_nnz, tw);
 }

@@ -488,6 +488,90 @@ class Engine:
                                          C.byref(st)), self._h)
         return out_rc[:n], (out_conflict[:n] if want_conflict else None), st.as_dict()
 
+    # ------------------------------------------- select by decision (carry)
+    def select_batch(self, batch: EpochBatch, rc, want: int = _abi.RC_ABORT, src=None, out=None,
+                     txn_base: int = 0, nnz_base: int = 0, want_src: bool = True):
+        """The txns with rc[i] == want as a CSR, where the batch lives
+        (dcc_batch_select): returns (EpochBatch, src u32[txn_base + n] | None,
+        stats).  The selection goes to rows txn_base.. / accesses nnz_base.. of
+        `out`, an EpochBatch of arrays with room for it (its source indices to
+        out.meta["src"], allocated when absent); the returned batch is `out`
+        cut to [: txn_base + n + 1] / [: nnz_base + nnz], so whatever lies in
+        front of the bases is part of it.  out=None allocates room for the whole
+        batch behind the bases, numpy or torch to match the batch.  src:
+        u32[n_txn], the identities the selected txns carry instead of their
+        index.  A selection that does not fit raises DccError(DCC_ERANGE) with
+        the counts it needed in .needed."""
+        n, m = batch.n_txn, batch.nnz
+        dev = batch.on_device
+        has_tn = batch.start_tn is not None
+        if dev:
+            import torch
+            d = batch.offsets.device
+
+            def empty(k, like, wide):
+                dt = like.dtype if like is not None and like.element_size() == wide else \
+                    {8: torch.int64, 4: torch.int32, 1: torch.uint8}[wide]
+                return torch.empty(max(k, 1), dtype=dt, device=d)
+        else:
+            def empty(k, like, wide):
+                return np.empty(max(k, 1), {8: np.uint64, 4: np.uint32, 1: np.uint8}[wide])
+            rc = np.ascontiguousarray(rc, np.uint8)
+            src = None if src is None else np.ascontiguousarray(src, np.uint32)
+        if rc.shape[0] < n or (src is not None and src.shape[0] < n):
+            raise ValueError("select_batch: rc / src shorter than the epoch")
+        if out is None:
+            out = EpochBatch(empty(txn_base + n + 1, batch.offsets, 4), empty(nnz_base + m, batch.keys, 8),
+                             empty(nnz_base + m, None, 1),
+                             empty(txn_base + n, batch.start_tn, 8) if has_tn else None,
+                             empty(txn_base + n, batch.finish_tn, 8) if has_tn else None,
+                             empty(txn_base + n, batch.order, 8) if batch.order is not None else None)
+        if _itemsize(out.offsets) != 4 or _itemsize(out.keys) != 8 or _itemsize(out.acctype) != 1:
+            raise TypeError("select_batch: out holds u32 offsets, u64 keys and u8 access types")
+        for a in (out.start_tn, out.finish_tn, out.order):
+            if a is not None and _itemsize(a) != 8:
+                raise TypeError("select_batch: out timestamps / order are u64")
+        cap_txn = int(out.offsets.shape[0]) - 1 - txn_base
+        cap_nnz = min(int(out.keys.shape[0]), int(out.acctype.shape[0])) - nnz_base
+        per_txn = [out.start_tn if has_tn else None, out.finish_tn if has_tn else None,
+                   out.order if batch.order is not None else None]
+        o_src = None
+        if want_src:
+            o_src = out.meta.get("src")
+            if o_src is None:
+                o_src = out.meta["src"] = empty(txn_base + max(cap_txn, 0), None, 4)
+            per_txn.append(o_src)
+        for a in per_txn:
+            if a is not None:
+                cap_txn = min(cap_txn, int(a.shape[0]) - txn_base)
+        if cap_txn < 0 or cap_nnz < 0:
+            raise ValueError("select_batch: out ends before the bases")
+        so = _abi.SelectOut(cap_txn, cap_nnz, txn_base, nnz_base, _ptr(out.offsets), _ptr(out.keys),
+                            _ptr(out.acctype), _ptr(per_txn[0]), _ptr(per_txn[1]), _ptr(per_txn[2]),
+                            _ptr(o_src))
+        st = _abi.Stats()
+        b = batch.to_c()
+        ns, ms = C.c_uint64(0), C.c_uint64(0)
+        code = lib.dcc_batch_select(self._h, C.byref(b), _ptr(rc), want, _ptr(src), C.byref(so),
+                                    C.byref(ns), C.byref(ms), C.byref(st))
+        try:
+            _check(code, self._h)
+        except DccError as e:
+            e.needed = (int(ns.value), int(ms.value))
+            raise
+        tn, tm = txn_base + int(ns.value), nnz_base + int(ms.value)
+        cut = [None if a is None else a[:tn] for a in per_txn[:3]]
+        sel = EpochBatch(out.offsets[:tn + 1], out.keys[:tm], out.acctype[:tm], cut[0], cut[1], cut[2],
+                         {"src": o_src[:tn]} if want_src else {})
+        return sel, (o_src[:tn] if want_src else None), st.as_dict()
+
+    def held_from(self, batch: EpochBatch, rc):
+        """The requests of the txns that committed (rc == RC_RCOK) as (keys,
+        acctype): the held prefix that nowait_lock_epoch(held=...) and
+        calvin_order_epoch_held take for the next epoch."""
+        sel, _, _ = self.select_batch(batch, rc, want=_abi.RC_RCOK, want_src=False)
+        return sel.keys, sel.acctype
+
     def calvin_dispatch(self, wave, order=None):
         """Wave dispatch lists (dcc_calvin_dispatch): returns (wave_off u32[W+1],
         txn u32[n]) — txn[wave_off[w]:wave_off[w+1]] run in wave w."""
@@ -627,6 +711,10 @@ def calvin_alg_bytes(n_txn: int, nnz: int, with_order: bool, with_wave: bool) ->
 
 def nowait_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
     return int(lib.dcc_nowait_alg_bytes(n_txn, nnz, int(with_conflict)))
+
+
+def select_alg_bytes(n_txn: int, n_sel: int, nnz_sel: int, n_txn_arrays: int = 0) -> int:
+    return int(lib.dcc_select_alg_bytes(n_txn, n_sel, nnz_sel, n_txn_arrays))
 
 
 # ---------------------------------------------------------------- producers

@@ -477,6 +477,64 @@ int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const dcc_calvin
  * + 16 nnz (one lock-table slot per request) + N (RC) [+ 4N conflict]. */
 uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
 
+/* ------------------------------------------- select by decision (carry) */
+/* The next epoch from this one's decisions, where the batch lives: the txns
+ * with rc[i] == want (exact equality against any byte value: DCC_RC_ABORT for
+ * the retries, DCC_RC_RCOK for the rows still held, DCC_RC_WAIT for Calvin's
+ * waiters) are copied into the CSR `out`, in index order, each with its
+ * accesses in list order.  The reference hands an aborted txn back to its
+ * abort queue (system/abort_queue.cpp) and submits it again; here that is one
+ * call between two epochs, with no host copy of a device batch.
+ *   out             where the selection goes (below); its arrays must not
+ *                   overlap the batch
+ *   rc              [n_txn] decision bytes
+ *   src_in          [n_txn] or NULL: out->src gets src_in[i] instead of i, so
+ *                   identities compose over any number of retries
+ *   *out_n, *out_nnz  selected txns / accesses; always host memory; may be NULL
+ * rc, src_in and every array of `out` live where the batch lives: device
+ * memory with DCC_DEVICE_PTRS, host memory otherwise.  The batch may be in any
+ * compact form (DCC_KEYS_U32, DCC_ACCTYPE_2BIT, DCC_TN_U32); the output is
+ * always wide.  Txn length is unbounded (MAX_ROW_PER_TXN does not apply: the
+ * call moves data) and zero-length txns are kept.  The offsets are checked on
+ * the device before anything indexes with them: malformed ones give DCC_EINVAL.
+ * A selection larger than cap_txn / cap_nnz, or one whose nnz_base + accesses
+ * does not fit a uint32_t, gives DCC_ERANGE: nothing is written to `out`, and
+ * *out_n / *out_nnz report what was needed.  n_txn == 0 gives DCC_OK, zero
+ * counts and offsets[txn_base] = nnz_base.
+ * Chaining: retries first is select(batch, rc, DCC_RC_ABORT) into the front of
+ * the next epoch's arrays, the fresh txns copied in behind out_n / out_nnz;
+ * fresh first and retries appended through txn_base / nnz_base needs no host
+ * read in between.  select(batch, rc, DCC_RC_RCOK): out->keys / out->acctype
+ * with *out_nnz entries are a dcc_calvin_held as they stand.
+ * Local: no collective.  A dcc_init_multi context runs it on rank 0's GPU; a
+ * context with a communicator attached runs it as any other.  Pipelined OCC
+ * epochs in flight complete first.
+ * Stats: n_commit = selected txns, n_abort = the rest, alg_bytes
+ * (dcc_select_alg_bytes), device_ms, total_ms; with profiling phase_ms:
+ * 0 = counting pass, 1 = scan of the tile counts, 2 = scatter. */
+typedef struct dcc_select_out {
+  uint64_t cap_txn, cap_nnz;   /* room, in txns / accesses, counted from the bases below   */
+  uint64_t txn_base, nnz_base; /* selected txn q goes to row txn_base+q, its accesses
+                                  start at nnz_base + (accesses of selected txns before it) */
+  uint32_t* offsets;           /* [txn_base + cap_txn + 1]; offsets[txn_base] = nnz_base is
+                                  written too, so the result chains behind what is there   */
+  uint64_t* keys;              /* [nnz_base + cap_nnz]  always the wide form                */
+  uint8_t*  acctype;           /* [nnz_base + cap_nnz]  one byte per access                 */
+  uint64_t* start_tn, *finish_tn, *order; /* [txn_base + cap_txn] or NULL: gathered when the
+                                  batch has the array AND this pointer is set (u64 out)    */
+  uint32_t* src;               /* [txn_base + cap_txn] or NULL: source index of each txn   */
+} dcc_select_out;
+int dcc_batch_select(dcc_ctx* ctx, const dcc_batch* batch, const uint8_t* rc, uint8_t want,
+                     const uint32_t* src_in, const dcc_select_out* out,
+                     uint64_t* out_n, uint64_t* out_nnz, dcc_stats* out_stats);
+/* Algorithmic bytes of one select: 4(N+1) offsets + N (RC) read, 18 per
+ * selected access (key + type read and written), 4(n_sel+1) offsets written,
+ * 16 n_sel per per-txn array carried (start_tn, finish_tn, order: 8 B read and
+ * 8 B written; src is counted the same, a bound: 4 B written, 4 B read with
+ * src_in). */
+uint64_t dcc_select_alg_bytes(uint64_t n_txn, uint64_t n_sel, uint64_t nnz_sel,
+                              int n_txn_arrays /* tn/order/src arrays carried */);
+
 /* Wave dispatch: the wave levels of an epoch
  * (out_wave of dcc_calvin_order_epoch) as the lists a dispatcher releases:
  * out_txn[out_wave_off[w] .. out_wave_off[w+1]) = the txns of wave w in

@@ -1,0 +1,252 @@
+"""Closed loop over resident device batches: epoch e + 1 = aborted(e) ++ fresh
+txns, and for NO_WAIT held(e + 1) = the requests of committed(e).  Reports
+goodput: commits per second with the retries in the loop.
+
+    python tools/retry_loop.py [--alg nowait|occ] [--epochs 8] [--fresh 65536] [--theta 0.9]
+                               [--loop-warmup 1] [--loop-reps 3]
+                               [--select-shapes both|c2|headline|none] [--warmup 5] [--steps 20]
+                               [--json PATH]
+
+The loop runs twice in one process on the same pre-generated fresh txns
+(gen_ycsb, already on the device, so the loop times the engine and the carry,
+not the generator):
+  path A  carries with dcc_batch_select (Engine.select_batch / held_from):
+          nothing but the two counts crosses to the host;
+  path B  carries on the host: rc to the host, a numpy build of the next epoch
+          and of the held rows, EpochBatch.to_torch back to the device.
+Per path: wall ms per epoch as median [min, max] over the timed passes, the
+goodput, and for path A the select's own device_ms and alg_bytes / device_ms.
+Both paths must produce the same rc sequence.
+
+--select-shapes times dcc_batch_select alone on the C2 (65,536 x 16) and the
+headline (1,048,576 x 16) YCSB epoch at theta 0.9 with that epoch's NO_WAIT rc,
+want = ABORT and want = RCOK, next to dcc_copy_bandwidth over the same byte
+count (alternately, same process), and the per-pass times of a profiled call."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import deneva_amd as d  # noqa: E402
+from deneva_amd import RC_ABORT, RC_RCOK, _abi  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def mmm(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
+
+
+def fmt(m):
+    return f"{m['median']:.3f} [{m['min']:.3f}, {m['max']:.3f}]"
+
+
+def dev_batch(b):
+    """Device batch with torch's signed dtypes (i32 offsets, i64 keys)."""
+    return d.EpochBatch(torch.from_numpy(b.offsets.view(np.int32)).to(DEV),
+                        torch.from_numpy(b.keys.view(np.int64)).to(DEV), torch.from_numpy(b.acctype).to(DEV))
+
+
+def copy_ms(eng, traffic_bytes):
+    """The engine's device copy moving `traffic_bytes` in all (read + written)."""
+    g = C.c_double(0)
+    code = _abi.lib.dcc_copy_bandwidth(eng.handle, max(traffic_bytes // 2, 16), 1, C.byref(g))
+    assert code == 0
+    return traffic_bytes / (g.value * 1e9) * 1e3
+
+
+# ------------------------------------------------------------ select alone
+def time_select(eng, n, a):
+    b = d.gen_ycsb(n_txn=n, zipf_theta=0.9)
+    db = dev_batch(b)
+    eng.reserve(b.n_txn, b.nnz)
+    rc = eng.nowait_lock_epoch(db, want_conflict=False)[0]
+    out = d.EpochBatch(torch.empty(n + 1, dtype=torch.int32, device=DEV),
+                       torch.empty(b.nnz, dtype=torch.int64, device=DEV),
+                       torch.empty(b.nnz, dtype=torch.uint8, device=DEV))
+    res = {}
+    for name, want in (("abort", RC_ABORT), ("rcok", RC_RCOK)):
+        def sel():
+            return eng.select_batch(db, rc, want, out=out)[2]
+        for _ in range(a.warmup):
+            st = sel()
+            copy_ms(eng, st["alg_bytes"])
+        ms, cp = [], []
+        for _ in range(a.steps):  # alternately: both see the same machine state
+            st = sel()
+            ms.append(st["device_ms"])
+            cp.append(copy_ms(eng, st["alg_bytes"]))
+        eng.set_profiling(True)
+        ph = [sel()["phase_ms"] for _ in range(5)]
+        eng.set_profiling(False)
+        r = {"selected": st["n_commit"], "selected_frac": st["n_commit"] / n, "alg_bytes": st["alg_bytes"],
+             "device_ms": mmm(ms), "copy_ms": mmm(cp),
+             "alg_GBps": st["alg_bytes"] / (statistics.median(ms) * 1e-3) / 1e9,
+             "select_over_copy": statistics.median(ms) / statistics.median(cp),
+             "pass_ms": {k: statistics.median(p[q] for p in ph) for q, k in enumerate(("count", "scan", "scatter"))}}
+        res[name] = r
+        print(f"  want={name:5s} selected {r['selected']} ({100 * r['selected_frac']:.1f} %)  device_ms "
+              f"{fmt(r['device_ms'])}  {r['alg_GBps']:.0f} GB/s  copy_ms {fmt(r['copy_ms'])}  select/copy "
+              f"{r['select_over_copy']:.2f}  passes {({k: round(v, 4) for k, v in r['pass_ms'].items()})}")
+    return res
+
+
+# ------------------------------------------------------------- closed loop
+def decide(eng, alg, cur, held):
+    if alg == "nowait":
+        rc, _, st = eng.nowait_lock_epoch(cur, held=held, want_conflict=False)
+    else:
+        rc, _, st = eng.occ_validate_epoch(cur)
+    return rc, st
+
+
+def loop_device(eng, alg, fresh_dev, E, bufs, timed):
+    """Path A.  bufs: two sets of arrays the epochs alternate between."""
+    F = fresh_dev[0].n_txn
+    cur, held = fresh_dev[0], None
+    wall, rcs, commits, sel_stats = [], [], 0, []
+    for e in range(E):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc, st = decide(eng, alg, cur, held)
+        commits += st["n_commit"]
+        if e + 1 < E:
+            nf = fresh_dev[e + 1]
+            if alg == "nowait":
+                held = eng.held_from(cur, rc)
+            out = bufs[e & 1]
+            sel, _, sst = eng.select_batch(cur, rc, RC_ABORT, out=out, want_src=False)
+            n0, m0 = sel.n_txn, sel.nnz
+            torch.add(nf.offsets[1:], m0, out=out.offsets[n0 + 1:n0 + 1 + F])
+            out.keys[m0:m0 + nf.nnz].copy_(nf.keys)
+            out.acctype[m0:m0 + nf.nnz].copy_(nf.acctype)
+            cur = d.EpochBatch(out.offsets[:n0 + F + 1], out.keys[:m0 + nf.nnz], out.acctype[:m0 + nf.nnz])
+            sel_stats.append(sst)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        if not timed:
+            rcs.append(rc.cpu().numpy().copy())
+    return wall, rcs, commits, sel_stats
+
+
+def loop_host(eng, alg, fresh, E, timed):
+    """Path B: the carry of tests/test_gpu_nowait.py::test_held_rows_carried_over_epochs."""
+    h = fresh[0]
+    cur, held = h.to_torch(DEV), None
+    wall, rcs, commits = [], [], 0
+    for e in range(E):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc, st = decide(eng, alg, cur, held)
+        commits += st["n_commit"]
+        hrc = rc.cpu().numpy()
+        if e + 1 < E:
+            nf = fresh[e + 1]
+            lens = np.diff(h.offsets.astype(np.int64))
+            ab = hrc == RC_ABORT
+            per_req = np.repeat(ab, lens)
+            if alg == "nowait":
+                ok = np.repeat(hrc == RC_RCOK, lens)
+                held = (torch.from_numpy(h.keys[ok].view(np.int64)).to(DEV), torch.from_numpy(h.acctype[ok]).to(DEV))
+            off = np.concatenate([[0], np.cumsum(lens[ab])])
+            m0 = int(off[-1])
+            h = d.EpochBatch(np.concatenate([off, nf.offsets[1:].astype(np.int64) + m0]).astype(np.uint32),
+                             np.concatenate([h.keys[per_req], nf.keys]),
+                             np.concatenate([h.acctype[per_req], nf.acctype]))
+            cur = h.to_torch(DEV)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        if not timed:
+            rcs.append(hrc.copy())
+    return wall, rcs, commits
+
+
+def closed_loop(eng, a):
+    E, F = a.epochs, a.fresh
+    fresh = [d.gen_ycsb(n_txn=F, zipf_theta=a.theta, seed=1000 + e) for e in range(E)]
+    fresh_dev = [dev_batch(b) for b in fresh]
+    cap_n, cap_m = E * F, sum(b.nnz for b in fresh)
+    eng.reserve(cap_n, cap_m)
+    bufs = [d.EpochBatch(torch.empty(cap_n + 1, dtype=torch.int32, device=DEV),
+                         torch.empty(cap_m, dtype=torch.int64, device=DEV),
+                         torch.empty(cap_m, dtype=torch.uint8, device=DEV)) for _ in range(2)]
+    # one untimed pass per path records the rc sequences
+    _, rc_a, _, _ = loop_device(eng, a.alg, fresh_dev, E, bufs, timed=False)
+    _, rc_b, _ = loop_host(eng, a.alg, fresh, E, timed=False)
+    same = len(rc_a) == len(rc_b) and all(np.array_equal(x, y) for x, y in zip(rc_a, rc_b))
+    for _ in range(max(a.loop_warmup - 1, 0)):
+        loop_device(eng, a.alg, fresh_dev, E, bufs, timed=True)
+        loop_host(eng, a.alg, fresh, E, timed=True)
+    wa, wb, ca, cb, sst = [], [], 0, 0, []
+    for _ in range(a.loop_reps):  # alternately
+        w, _, c, s = loop_device(eng, a.alg, fresh_dev, E, bufs, timed=True)
+        wa += w
+        ca += c
+        sst += s
+        w, _, c = loop_host(eng, a.alg, fresh, E, timed=True)
+        wb += w
+        cb += c
+    res = {"alg": a.alg, "epochs": E, "fresh": F, "theta": a.theta, "rc_identical": bool(same),
+           "txns_per_epoch": [int(r.size) for r in rc_a],
+           "commits_per_epoch": [int((r == RC_RCOK).sum()) for r in rc_a],
+           "A_select": {"wall_ms_per_epoch": mmm(wa), "goodput_commits_per_s": ca / (sum(wa) * 1e-3),
+                        "select_device_ms": mmm([s["device_ms"] for s in sst]),
+                        "select_alg_GBps": statistics.median(s["alg_bytes"] / (s["device_ms"] * 1e-3) / 1e9
+                                                             for s in sst)},
+           "B_host": {"wall_ms_per_epoch": mmm(wb), "goodput_commits_per_s": cb / (sum(wb) * 1e-3)}}
+    res["wall_B_over_A"] = res["B_host"]["wall_ms_per_epoch"]["median"] / res["A_select"]["wall_ms_per_epoch"]["median"]
+    res["goodput_A_over_B"] = res["A_select"]["goodput_commits_per_s"] / res["B_host"]["goodput_commits_per_s"]
+    print(f"closed loop {a.alg}: {E} epochs of {F} fresh txns, theta {a.theta}; txns per epoch "
+          f"{res['txns_per_epoch']}, commits {res['commits_per_epoch']}")
+    for k in ("A_select", "B_host"):
+        r = res[k]
+        print(f"  {k:9s} wall ms/epoch {fmt(r['wall_ms_per_epoch'])}  goodput {r['goodput_commits_per_s'] / 1e6:.2f} M commits/s"
+              + (f"  select device_ms {fmt(r['select_device_ms'])}  {r['select_alg_GBps']:.0f} GB/s"
+                 if "select_device_ms" in r else ""))
+    print(f"  wall B / A = {res['wall_B_over_A']:.2f}  goodput A / B = {res['goodput_A_over_B']:.2f}  "
+          f"rc identical {res['rc_identical']}")
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--alg", choices=("nowait", "occ"), default="nowait")
+    ap.add_argument("--epochs", type=int, default=8)
+    ap.add_argument("--fresh", type=int, default=65536)
+    ap.add_argument("--theta", type=float, default=0.9)
+    ap.add_argument("--loop-warmup", type=int, default=1)
+    ap.add_argument("--loop-reps", type=int, default=3)
+    ap.add_argument("--select-shapes", choices=("both", "c2", "headline", "none"), default="both")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "retry_loop needs cuda:0"
+    out = {}
+    with d.Engine(0) as eng:
+        for name, n, key in (("C2 65,536 x 16", 65536, "c2"), ("headline 1,048,576 x 16", 1 << 20, "headline")):
+            if a.select_shapes in ("both", key):
+                print(f"select alone, {name}:")
+                out[f"select {name}"] = time_select(eng, n, a)
+    with d.Engine(0) as eng:
+        if a.epochs > 0:
+            out["closed_loop"] = closed_loop(eng, a)
+    print(json.dumps(out))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+    assert out.get("closed_loop", {}).get("rc_identical", True), "the two carries gave different rc sequences"
+
+
+if __name__ == "__main__":
+    main()
