@@ -50,17 +50,6 @@
 
 using namespace dcc;
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 namespace {
 // helper workgroups of the wave walk (calvin_wave.hip), each on a CU of its
 // own (experiments builds: DCC_CW_HELPERS, 0 = the walker's workgroup alone;
@@ -997,11 +986,10 @@ static int calvin_sort_and_scan(dcc_ctx* ctx, const DevBatch& d, const uint32_t*
 int dcc_ctx::calvin_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint32_t* out_group,
                           uint8_t* out_rc, uint32_t* out_wave, dcc_stats* st) {
   dcc_ctx* ctx = this;
-  const auto t_wall0 = std::chrono::steady_clock::now();
+  EpochStats es;
+  dcc_stats& S = es.S;
   CR(check_batch(b));
   const bool dev_out = (b->flags & DCC_DEVICE_PTRS) != 0;
-  dcc_stats S;
-  memset(&S, 0, sizeof S);
   S.n_shards = (uint32_t)comm_ranks();
   if (b->n_txn == 0) {
     if (st) *st = S;
@@ -1020,21 +1008,9 @@ int dcc_ctx::calvin_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint3
   DevBatch d;
   CR(stage_batch(b, d));
   // the held prefix: device arrays alongside a device batch, else uploaded
-  const uint64_t* hkeys = nullptr;
-  const uint8_t* hat = nullptr;
-  if (nh) {
-    if (dev_out) {
-      hkeys = held->keys;
-      hat = held->acctype;
-    } else {
-      CR(cv_hkeys.ensure(this, nh * 8, "calvin held keys"));
-      CR(cv_hat.ensure(this, nh, "calvin held types"));
-      CK(hipMemcpyAsync(cv_hkeys.p, held->keys, nh * 8, hipMemcpyHostToDevice, stream));
-      CK(hipMemcpyAsync(cv_hat.p, held->acctype, nh, hipMemcpyHostToDevice, stream));
-      hkeys = (const uint64_t*)cv_hkeys.p;
-      hat = (const uint8_t*)cv_hat.p;
-    }
-  }
+  const uint64_t* hkeys;
+  const uint8_t* hat;
+  CR(stage_held(held, dev_out, hkeys, hat));
   // ---- outputs / workspaces (they depend on the shape only)
   CR(rc.ensure(this, d.n + 16, "rc"));
   uint8_t* rc_dev = (dev_out && out_rc) ? out_rc : (uint8_t*)rc.p;
@@ -1388,25 +1364,14 @@ int dcc_ctx::calvin_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint3
     ready += c.ready;
     maxwave = std::max(maxwave, c.maxwave);
   }
-  float ms = 0;
-  CK(hipEventElapsedTime(&ms, ev0, ev1));
   S.rounds = waves ? maxwave + 1 : 0;
   S.n_commit = ready;
   S.n_abort = d.n - ready;
   S.nnz_w = nex;
   S.alg_bytes = dcc_calvin_alg_bytes(d.n, d.nnz, d.order != nullptr, waves);
-  S.device_ms = ms;
   S.fallback = use_cb ? 1u : 0u;  // Calvin: the grant groups came from the bucket path
-  if (profiling) {
-    float t[4] = {0, 0, 0, 0};
-    CK(hipEventElapsedTime(&t[0], pev[0], pev[1]));  // prep + rank + layout
-    CK(hipEventElapsedTime(&t[1], pev[1], pev[2]));  // key sort
-    CK(hipEventElapsedTime(&t[2], pev[2], pev[3]));  // group scan
-    CK(hipEventElapsedTime(&t[3], pev[3], pev[4]));  // waves
-    for (int q = 0; q < 4; q++) S.phase_ms[q] = t[q];
-  }
-  const auto t_wall1 = std::chrono::steady_clock::now();
-  S.total_ms = std::chrono::duration<double, std::milli>(t_wall1 - t_wall0).count();
+  // phases: 0 = prep + rank + layout, 1 = key sort, 2 = group scan, 3 = waves
+  CR(es.finish(this, 4));
   if (st) *st = S;
   return DCC_OK;
 }

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -19,11 +21,31 @@ struct SwShard;  // occ_kernels.h: one key-sharded sweep level's serial range
 struct dcc_ctx;
 
 
+// A grow-only device allocation, freed with its owner: moving hands the
+// memory over (the target's own is freed first), copying is not possible.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      cap = o.cap;
+      o.p = nullptr;
+      o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int ensure(dcc_ctx* c, size_t bytes, const char* what);
-  void release();
+  void release();  // free now (a table that is dropped or replaced)
 };
 
 // A batch as device pointers (aliases the caller's or the ctx's staging).
@@ -183,7 +205,8 @@ struct dcc_ctx {
   uint32_t fin_tag = 0;                          // k_fin's look-back tag of the last epoch
   DevBuf perm, calvin_a, calvin_b, calvin_c, calvin_d;  // Calvin workspaces
   DevBuf cv_scratch, cv_agg, cv_group, cv_wave, cv_pgx, cv_gsx, cv_gsize, cv_done, cv_maxl, cv_cwmax, cv_cwpos, cv_cwmark, cv_cwhot, cv_cwpa, cv_cwoa, cv_cwhelp, cv_cwrec2;
-  DevBuf cv_seq_b, cv_ok, cv_len, cv_off2, cv_tsum, cv_hkeys, cv_hat;
+  DevBuf cv_seq_b, cv_ok, cv_len, cv_off2, cv_tsum;
+  DevBuf held_keys, held_at;  // held rows of a host call (Calvin / NO_WAIT: stage_held)
   DevBuf cb_e, cb_out, cb_cnt, cb_small;           // Calvin bucket path (calvin_bucket.h)
   DevBuf snap_top, snap_aoff, snap_aidx, snap_cnt;  // captured-snapshot validation
   DevBuf mt_rk;                                  // MaaT row table: 32-B {key, last read, last write} slots
@@ -200,11 +223,11 @@ struct dcc_ctx {
   // GPU index (index.hip): key table, newest insert ordinal per key, rows
   DevBuf ix_keys, ix_ord, ix_rows, ix_cnt, wv_buf, ix_scr, wv_hbuf, wv_obuf;
   // NO_WAIT lock epoch (nowait.hip): counters, slot id per request, undecided
-  // lists (ping-pong), conflict ordinals and held rows of a host call
-  DevBuf nw_misc, nw_sid, nw_list, nw_conf, nw_hk, nw_ha;
-  // select by decision (select.hip): control words, tile pairs; rc / src_in
+  // lists (ping-pong), conflict ordinals of a host call
+  DevBuf nw_misc, nw_sid, nw_list, nw_conf;
+  // select by decision (select.hip): control words, tile pairs; rc, src_in
   // and the output arrays of a host call
-  DevBuf sel_misc, sel_part, sel_in, sel_out;
+  DevBuf sel_misc, sel_part, sel_rc, sel_src, sel_out;
   uint32_t ix_bits = 0;
   uint64_t ix_nkeys = 0, ix_nrows = 0;
   double ix_last_ms = 0;
@@ -223,7 +246,6 @@ struct dcc_ctx {
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);
-  std::vector<DevBuf*> all_bufs();
   int reserve_occ(uint64_t n, uint64_t nnz, uint64_t nnz_w, uint32_t tw);
   void list_geometry(uint64_t n, uint32_t tw, uint64_t& seg_ts, uint64_t& seg_es) const;
   static uint64_t table_capacity(uint64_t nnz_w);
@@ -240,6 +262,24 @@ struct dcc_ctx {
   // validates them on the device instead, inside its level-0 launch)
   int check_batch(const dcc_batch* b, bool scan_offsets = true);
   int stage_batch(const dcc_batch* b, DevBatch& d);
+  // One input array of a call as a device array: a host array (`dev` false)
+  // is copied into `buf` on `stream`, a device array is read in place.
+  template <typename T>
+  int stage(DevBuf& buf, const T* src, size_t bytes, bool dev, const char* what, const T*& out) {
+    if (dev) {
+      out = src;
+      return DCC_OK;
+    }
+    if (int e = buf.ensure(this, bytes, what)) return e;
+    if (bytes) {
+      const hipError_t he = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, stream);
+      if (he != hipSuccess) return hip_fail(he, what);
+    }
+    out = (const T*)buf.p;
+    return DCC_OK;
+  }
+  // the held rows of a Calvin / NO_WAIT epoch (none: null arrays)
+  int stage_held(const dcc_calvin_held* held, bool dev, const uint64_t*& keys, const uint8_t*& at);
   int device_prep(const DevBatch& d, uint32_t& maxlen, uint64_t& nnz_w, uint64_t p = 0,
                   uint64_t* nnz_w_prefix = nullptr);
   int read_partials(size_t bytes);
@@ -350,6 +390,46 @@ struct dcc_ctx {
   int shard_groups(const uint32_t* grp, uint64_t m, uint32_t* out_dev);  // groups to batch order
 };
 
+// The host-side return-on-failure frame: CK takes a HIP call (the message goes
+// to `ctx`, a dcc_ctx* in scope), CR a call that returns a DCC code.
+#define CK(expr)                                           \
+  do {                                                     \
+    hipError_t e_ = (expr);                                \
+    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
+  } while (0)
+#define CR(expr)                 \
+  do {                           \
+    int r_ = (expr);             \
+    if (r_ != DCC_OK) return r_; \
+  } while (0)
+
+// The stats of a single-GPU epoch: constructed first thing (the wall clock
+// starts, S is zeroed with one shard), finished after the epoch's last
+// synchronisation.
+struct EpochStats {
+  dcc_stats S;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  EpochStats() {
+    memset(&S, 0, sizeof S);
+    S.n_shards = 1;
+  }
+  void wall() {
+    S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  // device_ms from ev0 / ev1, phase_ms[0, phases) from pev when profiling, total_ms
+  int finish(dcc_ctx* ctx, int phases) {
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    S.device_ms = ms;
+    for (int q = 0; ctx->profiling && q < phases; q++) {
+      CK(hipEventElapsedTime(&ms, ctx->pev[q], ctx->pev[q + 1]));
+      S.phase_ms[q] = ms;
+    }
+    wall();
+    return DCC_OK;
+  }
+};
+
 // multi-GPU context (dcc_multi.cpp)
 int dcc_multi_size(const dcc_ctx* ctx);
 void dcc_multi_destroy(dcc_ctx* ctx);
@@ -365,3 +445,17 @@ dcc_ctx* dcc_multi_rank0(dcc_ctx* ctx);  // rank 0's sub-context, its device sel
 void dcc_pipe_drain(dcc_ctx* ctx);
 void dcc_pipe_destroy(dcc_ctx* ctx);
 dcc_ctx* dcc_multi_sub(dcc_ctx* ctx, int rank);
+
+// A single-GPU engine's call on a multi-GPU context: run on rank 0's
+// sub-context with its device selected -- `detach`: without its communicator,
+// so that the engine makes no collective -- and the failure text copied up.
+template <typename F>
+int dcc_multi_on_rank0(dcc_ctx* ctx, bool detach, F call) {
+  dcc_ctx* s = dcc_multi_rank0(ctx);
+  dcc_comm_state* const cm = s->comm;
+  if (detach) s->comm = nullptr;
+  const int e = call(s);
+  s->comm = cm;
+  if (e != DCC_OK) ctx->last_error = s->last_error;
+  return e;
+}

@@ -57,17 +57,6 @@ void DevBuf::release() {
   cap = 0;
 }
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)             \
-  do {                       \
-    int r_ = (expr);         \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 static uint64_t next_pow2(uint64_t x) {
   uint64_t p = 1;
   while (p < x) p <<= 1;
@@ -164,7 +153,6 @@ extern "C" void dcc_destroy(dcc_ctx* ctx) {
   if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
   if (ctx->cv_graph_exec) (void)hipGraphExecDestroy(ctx->cv_graph_exec);
   dcc_comm_destroy(ctx);
-  for (DevBuf* b : ctx->all_bufs()) b->release();
   if (ctx->hmisc) (void)hipHostFree(ctx->hmisc);
   if (ctx->hpart) (void)hipHostFree(ctx->hpart);
   if (ctx->hdyn) (void)hipHostFree(ctx->hdyn);
@@ -175,7 +163,7 @@ extern "C" void dcc_destroy(dcc_ctx* ctx) {
   for (auto& e : ctx->pev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;  // every DevBuf member frees its device memory here
 }
 
 extern "C" int dcc_set_profiling(dcc_ctx* ctx, int enable) {
@@ -267,36 +255,6 @@ extern "C" int dcc_set_stream(dcc_ctx* ctx, void* s) {
   return DCC_OK;
 }
 
-std::vector<DevBuf*> dcc_ctx::all_bufs() {
-  std::vector<DevBuf*> v = {&misc, &part, &off, &keys, &acctype, &start_tn, &finish_tn, &table, &state,
-                            &hasw, &cflag, &bsum, &tn, &rc, &stat, &dyn, &fin_part,
-                            &order, &perm, &calvin_a, &calvin_b, &calvin_c, &calvin_d,
-                            &cv_scratch, &cv_agg, &cv_group, &cv_wave, &cv_pgx, &cv_gsx,
-                            &cv_gsize, &cv_done, &cv_maxl, &cv_cwmax, &cv_cwpos, &cv_cwmark, &cv_cwhot, &cv_cwpa, &cv_cwoa, &cv_cwhelp, &cv_cwrec2, &cv_seq_b, &cv_ok, &cv_len,
-                            &cv_off2, &cv_tsum, &cv_hkeys, &cv_hat, &cb_e, &cb_out, &cb_cnt, &cb_small, &gst, &hasw_scr, &sw_ctl, &sw_status, &sw_dbg,
-                            &sw_ckeys, &sw_gtab, &sw_rec, &sw_rk, &sw_fw, &sw_aent, &sw_mg, &sw_xcnt, &sw_xsend,
-                            &sw_xrec, &sw_mcnt, &sw_moff, &sw_mkeys, &sw_mat, &sw_kill,
-                            &sw_rflag, &sw_ro, &sw_wtab, &sw_cw, &sw_wtab_big,
-                            &snap_top, &snap_aoff, &snap_aidx, &snap_cnt, &mt_rk,
-                            &mt_misc, &mt_slot, &mt_sval, &mt_slot2, &mt_sval2, &mt_sfl,
-                            &mt_stx, &mt_txn, &mt_agg, &mt_sflB, &mt_stxB, &mt_k1, &mt_tcnt, &mt_ul, &mt_lb, &mt_ptab, &ix_keys, &ix_ord, &ix_rows, &ix_cnt, &wv_buf, &ix_scr, &wv_hbuf, &wv_obuf,
-                            &nw_misc, &nw_sid, &nw_list, &nw_conf, &nw_hk, &nw_ha,
-                            &sel_misc, &sel_part, &sel_in, &sel_out,
-                            &h_K[0], &h_K[1], &h_V[0], &h_V[1], &h_scr, &h_bsum, &h_bm,
-                            &nar_keys, &nar_at, &nar_tn, &fin_ctl, &fdyn, &fin_off, &fin_keys, &fin_at, &fin_state, &fin_hasw, &fin_rc, &fin_cnt,
-                            &sh_off, &sh_keys, &sh_at, &sh_src, &sh_cnt, &sh_bsum, &sh_rc, &sh_tn, &sh_grp};
-  for (auto& h : hs)
-    for (DevBuf* b : {&h.fk, &h.ft, &h.skey, &h.stn, &h.hash, &h.bm, &h.nx, &h.tcnt}) v.push_back(b);
-  for (auto& sb : sw_list)
-    for (DevBuf* b : {&sb.tid, &sb.off, &sb.keys, &sb.acctype, &sb.state}) v.push_back(b);
-  for (int i = 0; i < 2; i++) {
-    v.push_back(&l_tid[i]);
-    v.push_back(&l_coff[i]);
-    v.push_back(&l_cent[i]);
-  }
-  return v;
-}
-
 extern "C" int dcc_reserve(dcc_ctx* ctx, uint64_t max_txn, uint64_t max_nnz) {
   if (!ctx) return DCC_EINVAL;
   if (ctx->multi)
@@ -331,8 +289,7 @@ int dcc_ctx::hist_grow_flat(HistStore& h, uint64_t need) {
     CR(nb.ensure(this, want * w, "history pairs"));
     if (h.m) CK(hipMemcpyAsync(nb.p, b->p, h.m * w, hipMemcpyDeviceToDevice, stream));
     CK(hipStreamSynchronize(stream));
-    b->release();
-    *b = nb;
+    *b = std::move(nb);
   }
   return DCC_OK;
 }
@@ -573,12 +530,8 @@ extern "C" int dcc_occ_history_trim(dcc_ctx* ctx, uint64_t tn_floor) {
   CK(hipStreamSynchronize(ctx->stream));
   const uint64_t kept = *(const uint64_t*)ctx->hmisc;
   const uint64_t mx = std::max(B.max_tn, D.max_tn);
-  B.fk.release();
-  B.ft.release();
-  B.fk = N.fk;
-  B.ft = N.ft;
-  N.fk = DevBuf{};
-  N.ft = DevBuf{};
+  B.fk = std::move(N.fk);
+  B.ft = std::move(N.ft);
   B.m = kept;
   B.max_tn = mx;
   B.max_key = std::max(B.max_key, D.max_key);
@@ -702,13 +655,7 @@ int dcc_ctx::stage_batch(const dcc_batch* b, DevBatch& d) {
   w.nnz = d.nnz;
   w.n = d.n;
   // offsets: never compact (read in place from a device batch)
-  if (dev) {
-    d.off = b->offsets;
-  } else {
-    CR(off.ensure(this, (d.n + 1) * 4, "offsets"));
-    CK(hipMemcpyAsync(off.p, b->offsets, (d.n + 1) * 4, kind, stream));
-    d.off = (const uint32_t*)off.p;
-  }
+  CR(stage(off, b->offsets, (d.n + 1) * 4, dev, "offsets", d.off));
   CR(keys.ensure(this, std::max<uint64_t>(8, d.nnz * 8), "keys"));
   CR(acctype.ensure(this, std::max<uint64_t>(16, d.nnz), "acctype"));
   d.keys = (const uint64_t*)keys.p;
@@ -723,10 +670,8 @@ int dcc_ctx::stage_batch(const dcc_batch* b, DevBatch& d) {
       }
       w.k32 = (const uint32_t*)src;
       w.k64 = (uint64_t*)keys.p;
-    } else if (dev) {
-      d.keys = b->keys;
     } else {
-      CK(hipMemcpyAsync(keys.p, b->keys, d.nnz * 8, kind, stream));
+      CR(stage(keys, b->keys, d.nnz * 8, dev, "keys", d.keys));
     }
     if (a2) {
       const uint64_t pb = (d.nnz + 3) / 4;
@@ -738,10 +683,8 @@ int dcc_ctx::stage_batch(const dcc_batch* b, DevBatch& d) {
       }
       w.a2 = (const uint8_t*)src;
       w.a8 = (uint8_t*)acctype.p;
-    } else if (dev) {
-      d.acctype = b->acctype;
     } else {
-      CK(hipMemcpyAsync(acctype.p, b->acctype, d.nnz, kind, stream));
+      CR(stage(acctype, b->acctype, d.nnz, dev, "acctype", d.acctype));
     }
   }
   d.start_tn = d.finish_tn = nullptr;
@@ -763,29 +706,26 @@ int dcc_ctx::stage_batch(const dcc_batch* b, DevBatch& d) {
       w.f32 = (const uint32_t*)f0;
       w.s64 = (uint64_t*)start_tn.p;
       w.f64 = (uint64_t*)finish_tn.p;
-    } else if (dev) {
-      d.start_tn = b->start_tn;
-      d.finish_tn = b->finish_tn;
     } else {
-      CK(hipMemcpyAsync(start_tn.p, b->start_tn, d.n * 8, kind, stream));
-      CK(hipMemcpyAsync(finish_tn.p, b->finish_tn, d.n * 8, kind, stream));
+      CR(stage(start_tn, b->start_tn, d.n * 8, dev, "start_tn", d.start_tn));
+      CR(stage(finish_tn, b->finish_tn, d.n * 8, dev, "finish_tn", d.finish_tn));
     }
   }
   d.order = nullptr;
-  if (b->order) {
-    if (dev) {
-      d.order = b->order;
-    } else {
-      CR(order.ensure(this, d.n * 8, "order"));
-      CK(hipMemcpyAsync(order.p, b->order, d.n * 8, kind, stream));
-      d.order = (const uint64_t*)order.p;
-    }
-  }
+  if (b->order) CR(stage(order, b->order, d.n * 8, dev, "order", d.order));
   if (w.k32 || w.a2 || w.s32) {
     launch_widen(w, n_cu, stream);
     CK(hipGetLastError());
   }
   return DCC_OK;
+}
+
+int dcc_ctx::stage_held(const dcc_calvin_held* held, bool dev, const uint64_t*& hkeys, const uint8_t*& hat) {
+  hkeys = nullptr;
+  hat = nullptr;
+  if (!held || !held->n) return DCC_OK;
+  CR(stage(held_keys, held->keys, held->n * 8, dev, "held keys", hkeys));
+  return stage(held_at, held->acctype, held->n, dev, "held access types", hat);
 }
 
 extern "C" int dcc_copy_bandwidth(dcc_ctx* ctx, uint64_t bytes, int reps, double* gbps) {

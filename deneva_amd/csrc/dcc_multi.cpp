@@ -405,16 +405,16 @@ int dcc_multi_calvin_epoch(dcc_ctx* ctx, const dcc_batch* b, const dcc_calvin_he
     if (held && held->n) {
       // the shard's held rows go to its GPU beside its device batch
       const uint64_t nh = hk[r].size();
-      if ((x = s->cv_hkeys.ensure(s, std::max<uint64_t>(8, nh * 8), "calvin held keys")) != DCC_OK ||
-          (x = s->cv_hat.ensure(s, std::max<uint64_t>(16, nh), "calvin held types")) != DCC_OK)
+      if ((x = s->held_keys.ensure(s, std::max<uint64_t>(8, nh * 8), "calvin held keys")) != DCC_OK ||
+          (x = s->held_at.ensure(s, std::max<uint64_t>(16, nh), "calvin held types")) != DCC_OK)
         return x;
       hipError_t he = hipSuccess;
       if (nh) {
-        he = hipMemcpy(s->cv_hkeys.p, hk[r].data(), nh * 8, hipMemcpyHostToDevice);
-        if (he == hipSuccess) he = hipMemcpy(s->cv_hat.p, ha[r].data(), nh, hipMemcpyHostToDevice);
+        he = hipMemcpy(s->held_keys.p, hk[r].data(), nh * 8, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(s->held_at.p, ha[r].data(), nh, hipMemcpyHostToDevice);
       }
       if (he != hipSuccess) return s->hip_fail(he, "multi-GPU calvin: held rows in");
-      const dcc_calvin_held h{nh, (const uint64_t*)s->cv_hkeys.p, (const uint8_t*)s->cv_hat.p};
+      const dcc_calvin_held h{nh, (const uint64_t*)s->held_keys.p, (const uint8_t*)s->held_at.p};
       x = s->calvin_epoch(&sb, &h, dgrp, drc, nullptr, &S[r]);
     } else {
       x = s->calvin_epoch(&sb, nullptr, dgrp, drc, nullptr, &S[r]);

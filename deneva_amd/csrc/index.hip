@@ -27,17 +27,6 @@
 
 using namespace dcc;
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 namespace {
 
 __device__ inline uint64_t ix_hash(uint64_t key, uint32_t bits) {
@@ -175,15 +164,7 @@ int dcc_ctx::index_reserve(uint64_t want) {
   while ((1ull << bits) < 2 * want) bits++;
   if (bits > 34) return fail(DCC_ERANGE, "index: more than 2^33 keys");
   const uint64_t cap = 1ull << bits;
-  // the new table: released on every error return, moved in on success
-  DevBuf nk, no;
-  struct Guard {
-    DevBuf *a, *b;
-    ~Guard() {
-      if (a) a->release();
-      if (b) b->release();
-    }
-  } guard{&nk, &no};
+  DevBuf nk, no;  // the new table: moved in on success
   CR(nk.ensure(this, cap * 8, "index keys"));
   CR(no.ensure(this, cap * 8, "index ordinals"));
   CK(hipMemsetAsync(nk.p, 0xFF, cap * 8, stream));
@@ -194,11 +175,8 @@ int dcc_ctx::index_reserve(uint64_t want) {
         (uint64_t*)nk.p, (unsigned long long*)no.p, bits);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(stream));
-  ix_keys.release();
-  ix_ord.release();
-  ix_keys = nk;
-  ix_ord = no;
-  guard.a = guard.b = nullptr;
+  ix_keys = std::move(nk);
+  ix_ord = std::move(no);
   ix_bits = bits;
   return DCC_OK;
 }
@@ -216,8 +194,7 @@ extern "C" int dcc_index_insert(dcc_ctx* ctx, const uint64_t* keys, const uint64
     DevBuf nr;
     CR(nr.ensure(ctx, std::max<uint64_t>((base + n) * 8 * 3 / 2, 4096), "index rows"));
     if (base) CK(hipMemcpy(nr.p, ctx->ix_rows.p, base * 8, hipMemcpyDeviceToDevice));
-    ctx->ix_rows.release();
-    ctx->ix_rows = nr;
+    ctx->ix_rows = std::move(nr);
   }
   // host keys staged in the context's grow-only scratch (no per-call allocation)
   DevBuf& tk = ctx->ix_scr;

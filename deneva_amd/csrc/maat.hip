@@ -43,17 +43,6 @@
 
 using namespace dcc;
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 namespace {
 
 constexpr uint64_t U64MAX = ~0ull;
@@ -1038,8 +1027,7 @@ int dcc_ctx::maat_rows_reserve(uint64_t want) {
   CK(hipGetLastError());
   CK(hipMemcpyAsync(hmisc, cnt + 1, 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
-  mt_rk.release();
-  mt_rk = nt;
+  mt_rk = std::move(nt);
   mt_bits = bits;
   if (*(const uint32_t*)hmisc & MT_ERR_FULL) {  // a rehash walk ran past MT_WALK: bigger still
     CK(hipMemsetAsync(cnt + 1, 0, 4, stream));
@@ -1067,14 +1055,12 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
                             bool all_rows, bool* full) {
   dcc_ctx* ctx = this;
   *full = false;
-  const auto t_wall0 = std::chrono::steady_clock::now();
+  EpochStats es;
+  dcc_stats& S = es.S;
   CR(check_batch(b));
   if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "maat: single-GPU engine");
   const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
   const uint32_t rw_all = (b->flags & DCC_MAAT_READ_AND_PREWRITE) ? 1u : 0u;
-  dcc_stats S;
-  memset(&S, 0, sizeof S);
-  S.n_shards = 1;
   if (b->n_txn == 0) {
     if (st) *st = S;
     return DCC_OK;
@@ -1372,16 +1358,12 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
   if (hc[1] & MT_ERR_SPIN) return fail(DCC_EIO, "maat: round scan look-back timed out");
   if (hc[3]) return fail(DCC_EIO, "maat: %u undecided transactions", hc[3]);
   mt_new_last = mt_rows - rows_before;
-  float ms = 0;
-  CK(hipEventElapsedTime(&ms, ev0, ev1));
   S.rounds = rounds;
   S.n_commit = hc[2];
   S.n_abort = n - hc[2];
   S.nnz_w = hc[4];
   S.alg_bytes = dcc_maat_alg_bytes(n, m);
-  S.device_ms = ms;
-  S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0)
-                   .count();
+  CR(es.finish(this, 0));
   if (st) *st = S;
   return DCC_OK;
 }
@@ -1395,22 +1377,17 @@ extern "C" uint64_t dcc_maat_alg_bytes(uint64_t n_txn, uint64_t nnz) {
 extern "C" int dcc_maat_validate_epoch(dcc_ctx* ctx, const dcc_batch* batch, uint8_t* out_rc,
                                        uint64_t* out_commit_ts, dcc_stats* out_stats) {
   if (!ctx) return DCC_EINVAL;
-  if (ctx->multi) {  // the whole epoch on rank 0 (dcc_multi.cpp)
-    dcc_ctx* s = dcc_multi_rank0(ctx);
-    dcc_comm_state* const cm = s->comm;  // one GPU's engine: no collective
-    s->comm = nullptr;
-    const int e = s->maat_epoch(batch, out_rc, out_commit_ts, out_stats);
-    s->comm = cm;
-    if (e != DCC_OK) ctx->last_error = s->last_error;
-    return e;
-  }
+  if (ctx->multi)  // the whole epoch on rank 0 (dcc_multi.cpp): no collective
+    return dcc_multi_on_rank0(ctx, true, [&](dcc_ctx* s) {
+      return s->maat_epoch(batch, out_rc, out_commit_ts, out_stats);
+    });
   if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
   return ctx->maat_epoch(batch, out_rc, out_commit_ts, out_stats);
 }
 
 extern "C" int dcc_maat_rows_clear(dcc_ctx* ctx) {
   if (!ctx) return DCC_EINVAL;
-  if (ctx->multi) return dcc_maat_rows_clear(dcc_multi_rank0(ctx));
+  if (ctx->multi) return dcc_multi_on_rank0(ctx, false, dcc_maat_rows_clear);
   if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
   if (ctx->mt_bits) {
     const uint64_t cap = 1ull << ctx->mt_bits;
@@ -1425,7 +1402,9 @@ extern "C" int dcc_maat_rows_clear(dcc_ctx* ctx) {
 extern "C" int dcc_maat_rows_set(dcc_ctx* ctx, const uint64_t* keys, const uint64_t* last_read,
                                  const uint64_t* last_write, uint64_t n) {
   if (!ctx || (n && (!keys || !last_read || !last_write))) return DCC_EINVAL;
-  if (ctx->multi) return dcc_maat_rows_set(dcc_multi_rank0(ctx), keys, last_read, last_write, n);
+  if (ctx->multi)
+    return dcc_multi_on_rank0(ctx, false,
+                              [&](dcc_ctx* s) { return dcc_maat_rows_set(s, keys, last_read, last_write, n); });
   if (n == 0) return DCC_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
   CR(ctx->mt_misc.ensure(ctx, 64 + MT_RING * 4, "maat counters"));
@@ -1446,7 +1425,6 @@ extern "C" int dcc_maat_rows_set(dcc_ctx* ctx, const uint64_t* keys, const uint6
   uint32_t hc[2];
   CK(hipMemcpyAsync(hc, cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
   CK(hipStreamSynchronize(ctx->stream));
-  tmp.release();
   if (hc[1] & MT_ERR_KEY) return ctx->fail(DCC_EINVAL, "maat rows: key equal to DCC_KEY_RESERVED");
   if (hc[1] & MT_ERR_FULL) return ctx->fail(DCC_EIO, "maat: row table full");
   ctx->mt_rows = hc[0];
@@ -1456,7 +1434,9 @@ extern "C" int dcc_maat_rows_set(dcc_ctx* ctx, const uint64_t* keys, const uint6
 extern "C" int dcc_maat_rows_get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* last_read,
                                  uint64_t* last_write, uint64_t n) {
   if (!ctx || (n && (!keys || !last_read || !last_write))) return DCC_EINVAL;
-  if (ctx->multi) return dcc_maat_rows_get(dcc_multi_rank0(ctx), keys, last_read, last_write, n);
+  if (ctx->multi)
+    return dcc_multi_on_rank0(ctx, false,
+                              [&](dcc_ctx* s) { return dcc_maat_rows_get(s, keys, last_read, last_write, n); });
   if (n == 0) return DCC_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
   if (!ctx->mt_bits) {
@@ -1474,7 +1454,6 @@ extern "C" int dcc_maat_rows_get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* l
   CK(hipMemcpyAsync(last_read, t + n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
   CK(hipMemcpyAsync(last_write, t + 2 * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
   CK(hipStreamSynchronize(ctx->stream));
-  tmp.release();
   return DCC_OK;
 }
 

@@ -48,17 +48,6 @@
 
 using namespace dcc;
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 namespace {
 
 constexpr uint32_t NW_T = 256;        // threads per workgroup
@@ -398,16 +387,14 @@ int dcc_ctx::nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict) {
 int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
                           uint32_t* out_conflict, dcc_stats* st) {
   dcc_ctx* ctx = this;
-  const auto t_wall0 = std::chrono::steady_clock::now();
+  EpochStats es;
+  dcc_stats& S = es.S;
   if (!out_rc) return fail(DCC_EINVAL, "nowait: null out_rc");
   CR(check_batch(b, false));  // the offsets are checked on the device (k_nw_check)
   if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "nowait: single-GPU engine");
   const uint64_t hn = held ? held->n : 0;
   if (hn && (!held->keys || !held->acctype)) return fail(DCC_EINVAL, "nowait: null held keys/acctype");
   const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
-  dcc_stats S;
-  memset(&S, 0, sizeof S);
-  S.n_shards = 1;
   if (b->n_txn == 0) {
     if (st) *st = S;
     return DCC_OK;
@@ -454,16 +441,9 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   Slot* tab = (Slot*)table.p;
   CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
   if (hn) {
-    const uint64_t* hk = held->keys;
-    const uint8_t* ha = held->acctype;
-    if (!dev) {
-      CR(nw_hk.ensure(this, hn * 8, "nowait held keys"));
-      CR(nw_ha.ensure(this, hn, "nowait held access types"));
-      CK(hipMemcpyAsync(nw_hk.p, held->keys, hn * 8, hipMemcpyHostToDevice, stream));
-      CK(hipMemcpyAsync(nw_ha.p, held->acctype, hn, hipMemcpyHostToDevice, stream));
-      hk = (const uint64_t*)nw_hk.p;
-      ha = (const uint8_t*)nw_ha.p;
-    }
+    const uint64_t* hk;
+    const uint8_t* ha;
+    CR(stage_held(held, dev, hk, ha));
     k_nw_held<<<nw_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt);
   }
   NwArgs A{n, d.off, d.keys, d.acctype, tab, mask, lp, (uint32_t*)nw_sid.p, (uint8_t*)state.p, cnt};
@@ -527,22 +507,13 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   if (hc[NW_C_ERR] & NW_ERR_KEY) return fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
   if (hc[NW_C_ERR] & NW_ERR_FULL) return fail(DCC_EIO, "nowait: lock table full");
   if (hc[NW_C_ERR] & NW_ERR_STATE) return fail(DCC_EIO, "nowait: inconsistent decisions");
-  float ms = 0;
-  CK(hipEventElapsedTime(&ms, ev0, ev1));
-  if (prof)
-    for (int q = 0; q < 4; q++) {
-      float pm = 0;
-      CK(hipEventElapsedTime(&pm, pev[q], pev[q + 1]));
-      S.phase_ms[q] = pm;
-    }
   S.rounds = rounds;
   S.n_commit = hc[NW_C_COMMIT];
   S.n_abort = n - hc[NW_C_COMMIT];
   S.nnz_w = hc[NW_C_NEX];
   S.n_readonly = hc[NW_C_RO];
   S.alg_bytes = dcc_nowait_alg_bytes(n, m, out_conflict != nullptr);
-  S.device_ms = ms;
-  S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0).count();
+  CR(es.finish(this, 4));
   if (st) *st = S;
   return DCC_OK;
 }
@@ -557,15 +528,10 @@ extern "C" int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const
                                      uint8_t* out_rc, uint32_t* out_conflict, dcc_stats* out_stats) {
   if (!ctx || !batch || !out_rc) return DCC_EINVAL;
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
-  if (ctx->multi) {     // the whole epoch on rank 0 (the lock table is one GPU's)
-    dcc_ctx* s = dcc_multi_rank0(ctx);
-    dcc_comm_state* const cm = s->comm;  // one GPU's engine: no collective
-    s->comm = nullptr;
-    const int e = s->nowait_epoch(batch, held, out_rc, out_conflict, out_stats);
-    s->comm = cm;
-    if (e != DCC_OK) ctx->last_error = s->last_error;
-    return e;
-  }
+  if (ctx->multi)  // the whole epoch on rank 0 (the lock table is one GPU's): no collective
+    return dcc_multi_on_rank0(ctx, true, [&](dcc_ctx* s) {
+      return s->nowait_epoch(batch, held, out_rc, out_conflict, out_stats);
+    });
   if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
   return ctx->nowait_epoch(batch, held, out_rc, out_conflict, out_stats);
 }

@@ -21,17 +21,6 @@
 
 using namespace dcc;
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 static uint64_t next_pow2(uint64_t x) {
   uint64_t p = 1;
   while (p < x) p <<= 1;

@@ -305,23 +305,13 @@ __global__ __launch_bounds__(256) void k_snap(SnapArgs a) {
   }
 }
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 }  // namespace
 
 int dcc_ctx::occ_snapshot(const dcc_batch* b, const dcc_occ_snapshot* s, uint8_t* out_rc,
                           dcc_stats* st) {
   dcc_ctx* ctx = this;
-  const auto t_wall0 = std::chrono::steady_clock::now();
+  EpochStats es;
+  dcc_stats& S = es.S;
   if (!s || !s->active_off) return fail(DCC_EINVAL, "snapshot: null snapshot or active_off");
   // a device capture is not read on the host: its lists must be addressable
   if ((b && (b->flags & DCC_DEVICE_PTRS)) && !s->active_idx)
@@ -329,9 +319,6 @@ int dcc_ctx::occ_snapshot(const dcc_batch* b, const dcc_occ_snapshot* s, uint8_t
                             "when every list is empty)");
   if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "snapshot validation is single-GPU");
   CR(check_batch(b));
-  dcc_stats S;
-  memset(&S, 0, sizeof S);
-  S.n_shards = 1;
   if (b->n_txn == 0) {
     if (st) *st = S;
     return DCC_OK;
@@ -356,24 +343,14 @@ int dcc_ctx::occ_snapshot(const dcc_batch* b, const dcc_occ_snapshot* s, uint8_t
   }
   DevBatch d;
   CR(stage_batch(b, d));
-  const uint64_t* top = s->hist_top;
-  const uint32_t* aoff = s->active_off;
-  const uint32_t* aidx = s->active_idx;
-  if (!dev) {
-    CR(snap_aoff.ensure(this, (n + 1) * 4, "snapshot active_off"));
-    CR(snap_aidx.ensure(this, std::max<uint64_t>(16, n_active * 4), "snapshot active_idx"));
-    CK(hipMemcpyAsync(snap_aoff.p, aoff, (n + 1) * 4, hipMemcpyHostToDevice, stream));
-    if (n_active)
-      CK(hipMemcpyAsync(snap_aidx.p, aidx, n_active * 4, hipMemcpyHostToDevice, stream));
-    aoff = (const uint32_t*)snap_aoff.p;
-    aidx = (const uint32_t*)snap_aidx.p;
-    if (top) {
-      CR(snap_top.ensure(this, n * 8, "snapshot hist_top"));
-      CK(hipMemcpyAsync(snap_top.p, top, n * 8, hipMemcpyHostToDevice, stream));
-      top = (const uint64_t*)snap_top.p;
-    }
-    CR(rc.ensure(this, n + 16, "rc"));
-  }
+  const uint64_t* top = nullptr;
+  const uint32_t *aoff, *aidx;
+  CR(stage(snap_aoff, s->active_off, (n + 1) * 4, dev, "snapshot active_off", aoff));
+  // (a host capture with no active txn still hands the kernel an array)
+  if (!dev) CR(snap_aidx.ensure(this, 16, "snapshot active_idx"));
+  CR(stage(snap_aidx, s->active_idx, n_active * 4, dev, "snapshot active_idx", aidx));
+  if (s->hist_top) CR(stage(snap_top, s->hist_top, n * 8, dev, "snapshot hist_top", top));
+  if (!dev) CR(rc.ensure(this, n + 16, "rc"));
   const bool hist_on = d.start_tn && hist_size() > 0;
   if (hist_on) CR(hist_prepare());
   HistView hv{};
@@ -408,16 +385,12 @@ int dcc_ctx::occ_snapshot(const dcc_batch* b, const dcc_occ_snapshot* s, uint8_t
   CK(hipStreamSynchronize(stream));
   if (cnt[0])
     return fail(DCC_EINVAL, "snapshot: malformed device capture (error bits 0x%llx)", cnt[0]);
-  float ms = 0.f;
-  CK(hipEventElapsedTime(&ms, ev0, ev1));
   S.n_commit = cnt[1];
   S.n_abort = n - cnt[1];
   S.n_readonly = cnt[2];
   S.nnz_w = cnt[3];
   S.alg_bytes = cnt[4];
-  S.device_ms = ms;
-  S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0)
-                   .count();
+  CR(es.finish(this, 0));
   if (st) *st = S;
   return DCC_OK;
 }

@@ -34,17 +34,6 @@
 
 using namespace dcc;
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 namespace {
 
 constexpr uint32_t SEL_T = 256;  // threads per workgroup = txns per tile
@@ -236,7 +225,8 @@ int dcc_ctx::select_reserve(uint64_t n, uint64_t nnz) {
   CR(sel_misc.ensure(this, SEL_C_WORDS * 8, "select control words"));
   CR(sel_part.ensure(this, ((n + SEL_T - 1) / SEL_T + 1) * 8, "select tile pairs"));
   // a host call: rc and src_in in, every output array out
-  CR(sel_in.ensure(this, up16(n) + n * 4 + 16, "select rc / src"));
+  CR(sel_rc.ensure(this, n, "select rc"));
+  CR(sel_src.ensure(this, n * 4, "select src"));
   CR(sel_out.ensure(this, nnz * 8 + 3 * n * 8 + up16((n + 1) * 4) + n * 4 + nnz + 64, "select outputs"));
   return DCC_OK;
 }
@@ -244,7 +234,8 @@ int dcc_ctx::select_reserve(uint64_t n, uint64_t nnz) {
 int dcc_ctx::select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want, const uint32_t* src_in,
                           const dcc_select_out* out, uint64_t* out_n, uint64_t* out_nnz, dcc_stats* st) {
   dcc_ctx* ctx = this;
-  const auto t_wall0 = std::chrono::steady_clock::now();
+  EpochStats es;
+  dcc_stats& S = es.S;
   if (out_n) *out_n = 0;
   if (out_nnz) *out_nnz = 0;
   if (!out || !out->offsets) return fail(DCC_EINVAL, "select: null out / out offsets");
@@ -254,9 +245,6 @@ int dcc_ctx::select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want
   if (n && !rc_in) return fail(DCC_EINVAL, "select: null rc");
   if (out->nnz_base > 0xFFFFFFFFull) return fail(DCC_ERANGE, "select: nnz_base exceeds 2^32-1");
   const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
-  dcc_stats S;
-  memset(&S, 0, sizeof S);
-  S.n_shards = 1;
   if (n == 0) {
     const uint32_t v = (uint32_t)out->nnz_base;
     if (dev) {
@@ -267,7 +255,7 @@ int dcc_ctx::select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want
       out->offsets[out->txn_base] = v;
     }
     S.alg_bytes = dcc_select_alg_bytes(0, 0, 0, 0);
-    S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0).count();
+    es.wall();
     if (st) *st = S;
     return DCC_OK;
   }
@@ -300,9 +288,9 @@ int dcc_ctx::select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want
   uint64_t *h_keys = nullptr, *h_tn[3] = {};
   uint32_t *h_off = nullptr, *h_src = nullptr;
   uint8_t* h_at = nullptr;
+  CR(stage(sel_rc, rc_in, n, dev, "select rc", A.rc));
+  if (src_in) CR(stage(sel_src, src_in, n * 4, dev, "select src", A.src_in));
   if (dev) {
-    A.rc = rc_in;
-    A.src_in = src_in;
     A.o_off = out->offsets + out->txn_base;
     A.o_keys = out->keys ? out->keys + out->nnz_base : nullptr;
     A.o_at = out->acctype ? out->acctype + out->nnz_base : nullptr;
@@ -311,16 +299,8 @@ int dcc_ctx::select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want
     A.o_order = w_order ? out->order + out->txn_base : nullptr;
     A.o_src = w_src ? out->src + out->txn_base : nullptr;
   } else {
-    CR(sel_in.ensure(this, up16(n) + n * 4 + 16, "select rc / src"));
     CR(sel_out.ensure(this, room_m * 8 + 3 * room_n * 8 + up16((room_n + 1) * 4) + room_n * 4 + room_m + 64,
                       "select outputs"));
-    uint8_t* in = (uint8_t*)sel_in.p;
-    CK(hipMemcpyAsync(in, rc_in, n, hipMemcpyHostToDevice, stream));
-    A.rc = in;
-    if (src_in) {
-      CK(hipMemcpyAsync(in + up16(n), src_in, n * 4, hipMemcpyHostToDevice, stream));
-      A.src_in = (const uint32_t*)(in + up16(n));
-    }
     uint8_t* o = (uint8_t*)sel_out.p;
     h_keys = (uint64_t*)o;
     o += room_m * 8;
@@ -383,17 +363,8 @@ int dcc_ctx::select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want
     }
     CK(hipStreamSynchronize(stream));
   }
-  float ms_dev = 0;
-  CK(hipEventElapsedTime(&ms_dev, ev0, ev1));
-  if (prof)
-    for (int q = 0; q < 3; q++) {
-      float pm = 0;
-      CK(hipEventElapsedTime(&pm, pev[q], pev[q + 1]));
-      S.phase_ms[q] = pm;
-    }
   S.alg_bytes = dcc_select_alg_bytes(n, ns, ms, (int)w_start + (int)w_finish + (int)w_order + (int)w_src);
-  S.device_ms = ms_dev;
-  S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0).count();
+  CR(es.finish(this, 3));
   if (st) *st = S;
   return DCC_OK;
 }
@@ -411,12 +382,10 @@ extern "C" int dcc_batch_select(dcc_ctx* ctx, const dcc_batch* batch, const uint
                                 uint64_t* out_nnz, dcc_stats* out_stats) {
   if (!ctx || !batch) return DCC_EINVAL;
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
-  if (ctx->multi) {     // a local data movement: rank 0's GPU, no collective
-    dcc_ctx* s = dcc_multi_rank0(ctx);
-    const int e = s->select_batch(batch, rc, want, src_in, out, out_n, out_nnz, out_stats);
-    if (e != DCC_OK) ctx->last_error = s->last_error;
-    return e;
-  }
+  if (ctx->multi)  // a local data movement: rank 0's GPU, its communicator left alone
+    return dcc_multi_on_rank0(ctx, false, [&](dcc_ctx* s) {
+      return s->select_batch(batch, rc, want, src_in, out, out_n, out_nnz, out_stats);
+    });
   if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
   return ctx->select_batch(batch, rc, want, src_in, out, out_n, out_nnz, out_stats);
 }

@@ -19,17 +19,6 @@
 #include "dcc_scan.h"
 #include "radix_sort.h"
 
-#define CK(expr)                                           \
-  do {                                                     \
-    hipError_t e_ = (expr);                                \
-    if (e_ != hipSuccess) return ctx->hip_fail(e_, #expr); \
-  } while (0)
-#define CR(expr)                 \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != DCC_OK) return r_; \
-  } while (0)
-
 namespace {
 
 // dcc_key_shard (shard.cpp) on the device: splitmix64 finaliser, multiply-high
