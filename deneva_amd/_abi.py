@@ -41,6 +41,8 @@ ROW_NONE = 0xFFFFFFFFFFFFFFFF
 UNIQUE_ID_BYTES = 128
 # int (*)(void* user, uint8_t* host_buf, uint64_t n): in-place MAX all-reduce
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64)
+BACKOFF_REFERENCE, BACKOFF_NONE, BACKOFF_EXP = 0, 1, 2  # dcc_abortq_params.policy
+ABORTQ_SORT_FULL = 0x1
 OPT_RECHECK = 1
 OPT_BATCH_MAX = 2
 OPT_SOLVER = 5
@@ -97,6 +99,18 @@ class SelectOut(C.Structure):
         ("finish_tn", C.c_void_p),
         ("order", C.c_void_p),
         ("src", C.c_void_p),
+    ]
+
+
+class AbortqParams(C.Structure):
+    """dcc_abortq_params: room, penalty and policy of an abort queue."""
+    _fields_ = [
+        ("cap_txn", C.c_uint64),
+        ("cap_nnz", C.c_uint64),
+        ("penalty", C.c_uint64),
+        ("penalty_max", C.c_uint64),
+        ("policy", C.c_uint32),
+        ("flags", C.c_uint32),
     ]
 
 
@@ -254,6 +268,18 @@ _SIGS = [
      [_P, C.POINTER(Batch), _P, C.c_uint8, _P, C.POINTER(SelectOut), C.POINTER(C.c_uint64),
       C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     ("dcc_select_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]),
+    ("dcc_abortq_create", C.c_int, [_P, C.POINTER(AbortqParams), C.POINTER(C.c_void_p)]),
+    ("dcc_abortq_destroy", None, [_P]),
+    ("dcc_abortq_push", C.c_int,
+     [_P, C.POINTER(Batch), _P, C.c_uint8, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
+      C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    ("dcc_abortq_pop", C.c_int,
+     [_P, C.c_uint64, C.POINTER(SelectOut), _P, _P, C.c_uint32, C.POINTER(C.c_uint64),
+      C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    ("dcc_abortq_size", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("dcc_abortq_clear", C.c_int, [_P]),
+    ("dcc_abortq_push_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
+    ("dcc_abortq_pop_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     ("dcc_ycsb_params_default", None, [C.POINTER(YcsbParams)]),
     ("dcc_gen_ycsb", C.c_int, [C.POINTER(YcsbParams), _P, _P, _P, _P]),
     ("dcc_tpcc_params_default", None, [C.POINTER(TpccParams)]),

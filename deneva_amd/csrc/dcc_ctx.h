@@ -7,6 +7,7 @@
 
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -110,6 +111,25 @@ struct PeelInfo {
 // Dense survivor sub-batch of one peel level.
 struct SubBufs {
   DevBuf tid, off, keys, acctype, state;
+};
+
+// The device-resident abort queue (abortq.hip).  Two CSR pools with their
+// per-txn arrays: pushes append to pool `cur`, a pop compacts the kept entries
+// into the other one and swaps.  Pool order is seq (push) order.
+struct dcc_abortq {
+  dcc_ctx* owner = nullptr;  // the creating context (a multi-GPU one runs the work on rank 0)
+  dcc_abortq_params P{};
+  struct Pool {
+    DevBuf off, keys, at, src, cnt, due;
+  } pool[2];
+  DevBuf sk[2], sv[2], scratch;  // (due, pool index) pairs of the sort (ping-pong), its counts
+  DevBuf ctl, part;              // control words; tile pairs of the pop's three compactions
+  DevBuf st_cnt, st_out;         // cnt_in / the outputs of a host call
+  int cur = 0;
+  uint64_t n = 0, nnz = 0;  // parked txns / accesses
+  uint64_t seq = 0;         // txns pushed over the queue's life
+  uint64_t due_lo = ~0ull;  // a lower bound of every parked due: the smallest `now` pushed
+                            // with since the queue was last empty
 };
 
 struct dcc_ctx {
@@ -228,6 +248,8 @@ struct dcc_ctx {
   // select by decision (select.hip): control words, tile pairs; rc, src_in
   // and the output arrays of a host call
   DevBuf sel_misc, sel_part, sel_rc, sel_src, sel_out;
+  // abort queues created on this context and not yet destroyed (freed with it)
+  std::vector<std::unique_ptr<dcc_abortq>> abortqs;
   uint32_t ix_bits = 0;
   uint64_t ix_nkeys = 0, ix_nrows = 0;
   double ix_last_ms = 0;
@@ -383,6 +405,12 @@ struct dcc_ctx {
   int select_reserve(uint64_t n, uint64_t nnz);
   int select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want, const uint32_t* src_in,
                    const dcc_select_out* out, uint64_t* out_n, uint64_t* out_nnz, dcc_stats* st);
+  // abort queue (abortq.hip): the calls on the context that runs them
+  int abortq_alloc(dcc_abortq* q);
+  int abortq_push(dcc_abortq* q, const dcc_batch* b, const uint8_t* rc_in, uint8_t want, const uint32_t* src_in,
+                  const uint32_t* cnt_in, uint64_t now, uint64_t* out_n, uint64_t* out_nnz, dcc_stats* st);
+  int abortq_pop(dcc_abortq* q, uint64_t now, const dcc_select_out* out, uint32_t* out_cnt, uint64_t* out_due,
+                 uint32_t flags, uint64_t* out_n, uint64_t* out_nnz, dcc_stats* st);
   // device-side key-shard partition (shard_dev.hip): rank `rank` of R of a
   // multi-GPU context; sb is the shard as a device batch
   DevBuf sh_off, sh_keys, sh_at, sh_src, sh_cnt, sh_bsum, sh_rc, sh_tn, sh_grp;

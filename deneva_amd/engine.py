@@ -137,9 +137,13 @@ class Engine:
             raise DccError(code, f"dcc_init(device={device}, devices={devices}): "
                                  f"{_abi.strerror(code)} {detail}")
         self._h = h
+        self._queues = []  # AbortQueue objects alive on this context
 
     def close(self) -> None:
         if getattr(self, "_h", None):
+            for q in list(getattr(self, "_queues", [])):
+                q._q = None  # dcc_destroy frees the queues still alive
+            self._queues = []
             lib.dcc_destroy(self._h)
             self._h = None
 
@@ -565,6 +569,14 @@ class Engine:
                          {"src": o_src[:tn]} if want_src else {})
         return sel, (o_src[:tn] if want_src else None), st.as_dict()
 
+    # ------------------------------------ abort queue (back-off of the retries)
+    def abort_queue(self, cap_txn: int, cap_nnz: int, penalty: int, penalty_max: int,
+                    policy: int = _abi.BACKOFF_REFERENCE, flags: int = 0) -> "AbortQueue":
+        """A device-resident abort queue with room for cap_txn parked txns /
+        cap_nnz accesses (dcc_abortq_create): AbortQueue::enqueue / process of
+        system/abort_queue.cpp on the caller's clock."""
+        return AbortQueue(self, cap_txn, cap_nnz, penalty, penalty_max, policy, flags)
+
     def held_from(self, batch: EpochBatch, rc):
         """The requests of the txns that committed (rc == RC_RCOK) as (keys,
         acctype): the held prefix that nowait_lock_epoch(held=...) and
@@ -669,6 +681,138 @@ class Engine:
         _check(lib.dcc_comm_destroy(self._h), self._h)
 
 
+class AbortQueue:
+    """dcc_abortq: parked aborted txns in device memory (Engine.abort_queue)."""
+
+    def __init__(self, eng: "Engine", cap_txn: int, cap_nnz: int, penalty: int, penalty_max: int,
+                 policy: int, flags: int = 0):
+        self._eng = eng
+        self._q = None
+        self.cap_txn, self.cap_nnz = int(cap_txn), int(cap_nnz)
+        p = _abi.AbortqParams(cap_txn, cap_nnz, penalty, penalty_max, policy, flags)
+        h = C.c_void_p()
+        _check(lib.dcc_abortq_create(eng._h, C.byref(p), C.byref(h)), eng._h)
+        self._q = h
+        eng._queues.append(self)
+
+    def close(self) -> None:
+        if self._q is not None:
+            lib.dcc_abortq_destroy(self._q)
+            self._q = None
+            if self in self._eng._queues:
+                self._eng._queues.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if self._q is None:
+            raise ValueError("abort queue is closed")
+        return self._q
+
+    def push(self, batch: EpochBatch, rc, now: int, want: int = _abi.RC_ABORT, src=None, cnt=None):
+        """Park the txns with rc[i] == want at clock `now` (dcc_abortq_push):
+        returns (n, nnz, stats) of what was parked.  src / cnt: u32[n_txn], the
+        identities and abort counts the txns carry (their index / 0 when
+        None).  No room raises DccError(DCC_ERANGE) with .needed."""
+        n = batch.n_txn
+        if not batch.on_device:
+            rc = np.ascontiguousarray(rc, np.uint8)
+            src = None if src is None else np.ascontiguousarray(src, np.uint32)
+            cnt = None if cnt is None else np.ascontiguousarray(cnt, np.uint32)
+        for a in (rc, src, cnt):
+            if a is not None and a.shape[0] < n:
+                raise ValueError("push: rc / src / cnt shorter than the epoch")
+        for a in (src, cnt):
+            if a is not None and _itemsize(a) != 4:
+                raise TypeError("push: src / cnt are u32")
+        st = _abi.Stats()
+        b = batch.to_c()
+        ns, ms = C.c_uint64(0), C.c_uint64(0)
+        code = lib.dcc_abortq_push(self._handle(), C.byref(b), _ptr(rc), want, _ptr(src), _ptr(cnt), now,
+                                   C.byref(ns), C.byref(ms), C.byref(st))
+        try:
+            _check(code, self._eng._h)
+        except DccError as e:
+            e.needed = (int(ns.value), int(ms.value))
+            raise
+        return int(ns.value), int(ms.value), st.as_dict()
+
+    def pop(self, now: int, out=None, txn_base: int = 0, nnz_base: int = 0, device=None,
+            want_cnt: bool = True, want_due: bool = True):
+        """Release the entries with due < now, in (due, push) order, to rows
+        txn_base.. / accesses nnz_base.. of `out` (dcc_abortq_pop): returns
+        (EpochBatch, stats).  The batch is `out` cut to the bases plus the
+        counts; its meta carries "src", "cnt" and "due" (taken from out.meta,
+        allocated when absent; cnt / due are left out with want_cnt / want_due
+        False).  out=None allocates room for the whole queue behind the bases:
+        torch on `device` when given, numpy otherwise.  A release that does not
+        fit raises DccError(DCC_ERANGE) with .needed."""
+        qn, qm = self.size()
+        if out is not None:
+            dev = out.on_device
+            tdev = out.offsets.device if dev else None
+        else:
+            dev = device is not None
+            tdev = device
+        if dev:
+            import torch
+
+            def empty(k, wide):
+                return torch.empty(max(k, 1), dtype={8: torch.int64, 4: torch.int32, 1: torch.uint8}[wide],
+                                   device=tdev)
+        else:
+            def empty(k, wide):
+                return np.empty(max(k, 1), {8: np.uint64, 4: np.uint32, 1: np.uint8}[wide])
+        if out is None:
+            out = EpochBatch(empty(txn_base + qn + 1, 4), empty(nnz_base + qm, 8), empty(nnz_base + qm, 1))
+        if _itemsize(out.offsets) != 4 or _itemsize(out.keys) != 8 or _itemsize(out.acctype) != 1:
+            raise TypeError("pop: out holds u32 offsets, u64 keys and u8 access types")
+        cap_txn = int(out.offsets.shape[0]) - 1 - txn_base
+        cap_nnz = min(int(out.keys.shape[0]), int(out.acctype.shape[0])) - nnz_base
+        per = {}
+        for name, wide, on in (("src", 4, True), ("cnt", 4, want_cnt), ("due", 8, want_due)):
+            if not on:
+                per[name] = None
+                continue
+            a = out.meta.get(name)
+            if a is None:
+                a = out.meta[name] = empty(txn_base + max(cap_txn, 0), wide)
+            if _itemsize(a) != wide:
+                raise TypeError(f"pop: out.meta[{name!r}] has the wrong item size")
+            per[name] = a
+            cap_txn = min(cap_txn, int(a.shape[0]) - txn_base)
+        if cap_txn < 0 or cap_nnz < 0:
+            raise ValueError("pop: out ends before the bases")
+        so = _abi.SelectOut(cap_txn, cap_nnz, txn_base, nnz_base, _ptr(out.offsets), _ptr(out.keys),
+                            _ptr(out.acctype), None, None, None, _ptr(per["src"]))
+        st = _abi.Stats()
+        ns, ms = C.c_uint64(0), C.c_uint64(0)
+        code = lib.dcc_abortq_pop(self._handle(), now, C.byref(so), _ptr(per["cnt"]), _ptr(per["due"]),
+                                  _abi.DEVICE_PTRS if dev else 0, C.byref(ns), C.byref(ms), C.byref(st))
+        try:
+            _check(code, self._eng._h)
+        except DccError as e:
+            e.needed = (int(ns.value), int(ms.value))
+            raise
+        tn, tm = txn_base + int(ns.value), nnz_base + int(ms.value)
+        meta = {k: v[:tn] for k, v in per.items() if v is not None}
+        return EpochBatch(out.offsets[:tn + 1], out.keys[:tm], out.acctype[:tm], None, None, None, meta), \
+            st.as_dict()
+
+    def size(self):
+        """(parked txns, parked accesses): host state, no device work."""
+        n, m = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.dcc_abortq_size(self._handle(), C.byref(n), C.byref(m)), self._eng._h)
+        return int(n.value), int(m.value)
+
+    def clear(self) -> None:
+        _check(lib.dcc_abortq_clear(self._handle()), self._eng._h)
+
+
 def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(_abi.UNIQUE_ID_BYTES)
     _check(lib.dcc_comm_unique_id(buf))
@@ -718,6 +862,14 @@ def select_alg_bytes(n_txn: int, n_sel: int, nnz_sel: int, n_txn_arrays: int = 0
 
 
 # ---------------------------------------------------------------- producers
+def abortq_push_alg_bytes(n_txn: int, n_sel: int, nnz_sel: int) -> int:
+    return int(lib.dcc_abortq_push_alg_bytes(n_txn, n_sel, nnz_sel))
+
+
+def abortq_pop_alg_bytes(n_q: int, nnz_q: int, n_due: int, nnz_due: int) -> int:
+    return int(lib.dcc_abortq_pop_alg_bytes(n_q, nnz_q, n_due, nnz_due))
+
+
 def ycsb_params(**kw) -> _abi.YcsbParams:
     p = _abi.YcsbParams()
     lib.dcc_ycsb_params_default(C.byref(p))

@@ -484,7 +484,8 @@ uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
  * waiters) are copied into the CSR `out`, in index order, each with its
  * accesses in list order.  The reference hands an aborted txn back to its
  * abort queue (system/abort_queue.cpp) and submits it again; here that is one
- * call between two epochs, with no host copy of a device batch.
+ * call between two epochs, with no host copy of a device batch (retried at
+ * once; the queue's back-off is dcc_abortq_*, below).
  *   out             where the selection goes (below); its arrays must not
  *                   overlap the batch
  *   rc              [n_txn] decision bytes
@@ -534,6 +535,108 @@ int dcc_batch_select(dcc_ctx* ctx, const dcc_batch* batch, const uint8_t* rc, ui
  * src_in). */
 uint64_t dcc_select_alg_bytes(uint64_t n_txn, uint64_t n_sel, uint64_t nnz_sel,
                               int n_txn_arrays /* tn/order/src arrays carried */);
+
+/* ------------------------------------ abort queue (back-off of the retries) */
+/* The reference does not retry an aborted txn at once: WorkerThread bumps its
+ * abort_cnt and hands it to AbortQueue::enqueue (system/worker_thread.cpp:
+ * 165-168), which parks it until now + penalty(abort_cnt)
+ * (system/abort_queue.cpp:26-50); AbortQueue::process releases the entries
+ * with penalty_end < now in penalty_end order (:52-82, abort_queue.h:37-42).
+ * This is that queue where the batch lives: the parked txns stay in device
+ * memory, a push takes an epoch and its decisions, a pop writes the due txns
+ * as the front of the next epoch's CSR.
+ *
+ * An entry is (due u64, seq u64, src u32, cnt u32, accesses).  seq is the push
+ * ordinal over the queue's life; it is never stored: the pool is kept in seq
+ * order.  The clock `now` is the caller's (ns, epochs, anything monotone);
+ * nothing reads a real clock.
+ *
+ * Penalty, with cnt the abort count AFTER the increment (first abort: 1):
+ *   DCC_BACKOFF_NONE       penalty                          (BACKOFF false)
+ *   DCC_BACKOFF_REFERENCE  exactly what abort_queue.cpp:30 computes as C
+ *                          parses it, in u64: max((penalty * 2) ^ cnt,
+ *                          penalty_max) -- `^` is XOR and binds looser than
+ *                          `*`, and it is max.  penalty 10, penalty_max 5,
+ *                          cnt 1, 2, 3, 4, 5, 20: 21, 22, 23, 16, 17, 5.  With
+ *                          the reference's defaults (config.h:112-114) it is
+ *                          penalty_max for every realistic cnt.  The default.
+ *   DCC_BACKOFF_EXP        the evident intent: min(penalty * 2^cnt,
+ *                          penalty_max); penalty_max when cnt >= 64 or the
+ *                          shift loses bits.
+ * due = now + penalty(cnt), saturating at 2^64 - 1.
+ *
+ * Every buffer is allocated by dcc_abortq_create (both CSR pools, the per-txn
+ * arrays, the sort buffers): a warmed-up push or pop of a device batch
+ * allocates nothing.  The queue is always device-resident; on a
+ * dcc_init_multi context it lives on rank 0's GPU.  No call is a collective.
+ * Pipelined OCC epochs in flight complete first.  Work runs on the context's
+ * stream.  A queue still alive at dcc_destroy is freed with its context. */
+#define DCC_BACKOFF_REFERENCE 0
+#define DCC_BACKOFF_NONE 1
+#define DCC_BACKOFF_EXP 2
+/* dcc_abortq_params.flags */
+#define DCC_ABORTQ_SORT_FULL 0x1u /* pop sorts all 64 bits of `due` instead of only the bits
+                                     that can differ among the due entries (A/B timing)       */
+typedef struct dcc_abortq dcc_abortq;
+typedef struct dcc_abortq_params {
+  uint64_t cap_txn, cap_nnz; /* room, in parked txns / accesses; both < 2^32 */
+  uint64_t penalty;          /* ABORT_PENALTY, in the caller's clock units   */
+  uint64_t penalty_max;      /* ABORT_PENALTY_MAX                            */
+  uint32_t policy;           /* DCC_BACKOFF_*                                */
+  uint32_t flags;            /* DCC_ABORTQ_*                                 */
+} dcc_abortq_params;
+int dcc_abortq_create(dcc_ctx* ctx, const dcc_abortq_params* params, dcc_abortq** out);
+void dcc_abortq_destroy(dcc_abortq* q);
+/* Park the txns with rc[i] == want (the selection of dcc_batch_select: index
+ * order, accesses in list order, empty txns kept, any txn length, any compact
+ * batch form).  Entry: cnt = (cnt_in ? cnt_in[i] : 0) + 1, saturating at
+ * 2^32 - 1; src = src_in ? src_in[i] : i; due from the penalty, computed on
+ * the device.  rc / src_in / cnt_in live where the batch lives (device memory
+ * with DCC_DEVICE_PTRS).  Malformed offsets give DCC_EINVAL.  More than the
+ * queue's room, in txns or accesses, gives DCC_ERANGE: the queue is unchanged
+ * and *out_n / *out_nnz (host memory, may be NULL) report what was needed;
+ * otherwise they report what was parked.
+ * Stats: n_commit = parked txns, n_abort = the rest, alg_bytes
+ * (dcc_abortq_push_alg_bytes), device_ms, total_ms; with profiling phase_ms
+ * as the select's. */
+int dcc_abortq_push(dcc_abortq* q, const dcc_batch* batch, const uint8_t* rc, uint8_t want,
+                    const uint32_t* src_in, const uint32_t* cnt_in, uint64_t now,
+                    uint64_t* out_n, uint64_t* out_nnz, dcc_stats* out_stats);
+/* Release every entry with due < now (strict, abort_queue.cpp:62), in
+ * (due, seq) order, to rows out->txn_base.. / accesses out->nnz_base.. of
+ * `out`, exactly as a select writes them (offsets[txn_base] = nnz_base is
+ * written, the output is wide).  Their src goes to out->src; their cnt and
+ * due to out_cnt / out_due, [txn_base + cap_txn] each, or NULL.  start_tn /
+ * finish_tn / order of `out` are not written.  The other entries stay, in seq
+ * order.  flags: DCC_DEVICE_PTRS when the arrays of `out`, out_cnt and
+ * out_due are device memory; host memory otherwise.  A release that does not
+ * fit cap_txn / cap_nnz, or whose nnz_base + accesses exceeds 2^32 - 1, gives
+ * DCC_ERANGE: nothing is written, the queue is unchanged, *out_n / *out_nnz
+ * report what was needed.  Nothing due gives DCC_OK, zero counts and
+ * offsets[txn_base] = nnz_base.
+ * Stats: n_commit = released txns, n_abort = left parked, alg_bytes
+ * (dcc_abortq_pop_alg_bytes), device_ms, total_ms; with profiling phase_ms:
+ * 0 = due flags and counts, 1 = sort, 2 = gather of the released txns,
+ * 3 = compaction of the kept ones. */
+int dcc_abortq_pop(dcc_abortq* q, uint64_t now, const dcc_select_out* out, uint32_t* out_cnt,
+                   uint64_t* out_due, uint32_t flags, uint64_t* out_n, uint64_t* out_nnz,
+                   dcc_stats* out_stats);
+/* Parked txns / accesses: host state, no device work. */
+int dcc_abortq_size(const dcc_abortq* q, uint64_t* out_n, uint64_t* out_nnz);
+/* Drop every entry (the buffers stay). */
+int dcc_abortq_clear(dcc_abortq* q);
+/* Algorithmic bytes of a push: the select of the same txns with one per-txn
+ * array (src) plus 12 per parked txn (cnt 4 B and due 8 B written):
+ * dcc_select_alg_bytes(n_txn, n_sel, nnz_sel, 1) + 12 n_sel. */
+uint64_t dcc_abortq_push_alg_bytes(uint64_t n_txn, uint64_t n_sel, uint64_t nnz_sel);
+/* Algorithmic bytes of a pop of n_due txns / nnz_due accesses from a queue of
+ * n_q / nnz_q: due and offsets of every entry read (8 n_q + 4(n_q+1)), one
+ * (due, index) pair per entry written and read once (24 n_q; the radix
+ * passes in between are not counted), every access moved once (18 nnz_q: the
+ * released ones to `out`, the kept ones to the other pool), both offset
+ * arrays written (4(n_due+1) + 4(n_q-n_due+1)), src / cnt / due of every
+ * entry read and written (32 n_q).  Nothing due: the first term alone. */
+uint64_t dcc_abortq_pop_alg_bytes(uint64_t n_q, uint64_t nnz_q, uint64_t n_due, uint64_t nnz_due);
 
 /* Wave dispatch: the wave levels of an epoch
  * (out_wave of dcc_calvin_order_epoch) as the lists a dispatcher releases:

@@ -5,7 +5,8 @@ goodput: commits per second with the retries in the loop.
     python tools/retry_loop.py [--alg nowait|occ] [--epochs 8] [--fresh 65536] [--theta 0.9]
                                [--loop-warmup 1] [--loop-reps 3]
                                [--select-shapes both|c2|headline|none] [--warmup 5] [--steps 20]
-                               [--json PATH]
+                               [--backoff none|reference|exp --penalty P --penalty-max M]
+                               [--queue-shapes both|c2|headline|none] [--json PATH]
 
 The loop runs twice in one process on the same pre-generated fresh txns
 (gen_ycsb, already on the device, so the loop times the engine and the carry,
@@ -21,7 +22,20 @@ Both paths must produce the same rc sequence.
 --select-shapes times dcc_batch_select alone on the C2 (65,536 x 16) and the
 headline (1,048,576 x 16) YCSB epoch at theta 0.9 with that epoch's NO_WAIT rc,
 want = ABORT and want = RCOK, next to dcc_copy_bandwidth over the same byte
-count (alternately, same process), and the per-pass times of a profiled call."""
+count (alternately, same process), and the per-pass times of a profiled call.
+
+--backoff parks the aborted txns in an abort queue instead of retrying them at
+once (system/abort_queue.cpp), the clock being the epoch index: epoch e + 1 =
+pop(e + 1) ++ fresh txns.  Path A uses the device queue (Engine.abort_queue)
+and carries the epoch's src / cnt arrays on the device, the fresh txns getting
+0; path B does the same on the host with tests/abortq_ref.py.  Without
+--backoff the loop is the one above.
+
+--queue-shapes times the queue's push and pop alone on the same two epochs:
+the push of the aborted txns next to dcc_batch_select of the same selection
+and dcc_copy_bandwidth over the same bytes, a pop that releases all of them
+and one that releases about half (EXP, cnt 0 or 1 at random), the pop's
+phases, and the pop of all with the sort over all 64 bits."""
 import argparse
 import ctypes as C
 import json
@@ -100,6 +114,73 @@ def time_select(eng, n, a):
     return res
 
 
+# ------------------------------------------------------------- queue alone
+def time_queue(eng, n, a):
+    b = d.gen_ycsb(n_txn=n, zipf_theta=0.9)
+    db = dev_batch(b)
+    eng.reserve(b.n_txn, b.nnz)
+    rc = eng.nowait_lock_epoch(db, want_conflict=False)[0]
+    out = d.EpochBatch(torch.empty(n + 1, dtype=torch.int32, device=DEV),
+                       torch.empty(b.nnz, dtype=torch.int64, device=DEV),
+                       torch.empty(b.nnz, dtype=torch.uint8, device=DEV),
+                       meta={"src": torch.empty(n, dtype=torch.int32, device=DEV),
+                             "cnt": torch.empty(n, dtype=torch.int32, device=DEV),
+                             "due": torch.empty(n, dtype=torch.int64, device=DEV)})
+    cnt_in = torch.from_numpy(np.random.default_rng(5).integers(0, 2, size=n).astype(np.int32)).to(DEV)
+    torch.cuda.synchronize()
+    # EXP, penalty 1: cnt_in 0 -> due 2, cnt_in 1 -> due 4 (pushed at 0)
+    qs = {"varying": eng.abort_queue(n, b.nnz, 1, 1 << 40, _abi.BACKOFF_EXP),
+          "full": eng.abort_queue(n, b.nnz, 1, 1 << 40, _abi.BACKOFF_EXP, _abi.ABORTQ_SORT_FULL)}
+    q = qs["varying"]
+
+    def cycle(qq, now):
+        qq.clear()
+        pst = qq.push(db, rc, 0, cnt=cnt_in)[2]
+        return pst, qq.pop(now, out=out)[1]
+
+    def sel():
+        return eng.select_batch(db, rc, RC_ABORT, out=out)[2]
+    for _ in range(a.warmup):
+        pst, _ = cycle(q, 5)
+        cycle(q, 3)
+        cycle(qs["full"], 5)
+        sel()
+        copy_ms(eng, pst["alg_bytes"])
+    push, selm, cp, pop_all, pop_half, pop_full = [], [], [], [], [], []
+    for _ in range(a.steps):  # alternately: all see the same machine state
+        pst, ost = cycle(q, 5)
+        push.append(pst["device_ms"])
+        pop_all.append(ost["device_ms"])
+        selm.append(sel()["device_ms"])
+        cp.append(copy_ms(eng, pst["alg_bytes"]))
+        hst = cycle(q, 3)[1]
+        pop_half.append(hst["device_ms"])
+        pop_full.append(cycle(qs["full"], 5)[1]["device_ms"])
+    eng.set_profiling(True)
+    names = ("flags", "sort", "gather", "keep")
+    ph = {k: [cycle(qq, now)[1]["phase_ms"] for _ in range(5)]
+          for k, qq, now in (("all", q, 5), ("half", q, 3), ("all_sort64", qs["full"], 5))}
+    eng.set_profiling(False)
+    for qq in qs.values():
+        qq.close()
+    r = {"parked": pst["n_commit"], "parked_frac": pst["n_commit"] / n, "push_alg_bytes": pst["alg_bytes"],
+         "push_ms": mmm(push), "select_ms": mmm(selm), "copy_ms": mmm(cp),
+         "push_over_select": statistics.median(push) / statistics.median(selm),
+         "pop_all": {"released": ost["n_commit"], "alg_bytes": ost["alg_bytes"], "device_ms": mmm(pop_all)},
+         "pop_half": {"released": hst["n_commit"], "alg_bytes": hst["alg_bytes"], "device_ms": mmm(pop_half)},
+         "pop_all_sort64": {"device_ms": mmm(pop_full)},
+         "phase_ms": {k: {nm: statistics.median(p[i] for p in v) for i, nm in enumerate(names)}
+                      for k, v in ph.items()}}
+    print(f"  parked {r['parked']} ({100 * r['parked_frac']:.1f} %)  push {fmt(r['push_ms'])}  select "
+          f"{fmt(r['select_ms'])}  copy {fmt(r['copy_ms'])}  push/select {r['push_over_select']:.2f}")
+    print(f"  pop all ({r['pop_all']['released']}) {fmt(r['pop_all']['device_ms'])}  half "
+          f"({r['pop_half']['released']}) {fmt(r['pop_half']['device_ms'])}  all, 64-bit sort "
+          f"{fmt(r['pop_all_sort64']['device_ms'])}")
+    for k, v in r["phase_ms"].items():
+        print(f"    phases {k}: {({nm: round(x, 4) for nm, x in v.items()})}")
+    return r
+
+
 # ------------------------------------------------------------- closed loop
 def decide(eng, alg, cur, held):
     if alg == "nowait":
@@ -170,6 +251,133 @@ def loop_host(eng, alg, fresh, E, timed):
     return wall, rcs, commits
 
 
+def loop_device_backoff(eng, alg, fresh_dev, E, bufs, q, timed):
+    """Path A with the device abort queue; the clock is the epoch index."""
+    F = fresh_dev[0].n_txn
+    q.clear()
+    ids = [torch.arange(e * F, (e + 1) * F, dtype=torch.int32, device=DEV) for e in range(E)]
+    cur, held = fresh_dev[0], None
+    src, cnt = ids[0], torch.zeros(F, dtype=torch.int32, device=DEV)
+    wall, rcs, commits, q_stats = [], [], 0, []
+    for e in range(E):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc, st = decide(eng, alg, cur, held)
+        commits += st["n_commit"]
+        if e + 1 < E:
+            nf = fresh_dev[e + 1]
+            if alg == "nowait":
+                held = eng.held_from(cur, rc)
+            pst = q.push(cur, rc, e, src=src, cnt=cnt)[2]
+            out = bufs[e & 1]
+            got, ost = q.pop(e + 1, out=out, want_due=False)
+            n0, m0 = got.n_txn, got.nnz
+            torch.add(nf.offsets[1:], m0, out=out.offsets[n0 + 1:n0 + 1 + F])
+            out.keys[m0:m0 + nf.nnz].copy_(nf.keys)
+            out.acctype[m0:m0 + nf.nnz].copy_(nf.acctype)
+            out.meta["src"][n0:n0 + F].copy_(ids[e + 1])
+            out.meta["cnt"][n0:n0 + F].zero_()
+            cur = d.EpochBatch(out.offsets[:n0 + F + 1], out.keys[:m0 + nf.nnz], out.acctype[:m0 + nf.nnz])
+            src, cnt = out.meta["src"][:n0 + F], out.meta["cnt"][:n0 + F]
+            q_stats.append((pst, ost))
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        if not timed:
+            rcs.append(rc.cpu().numpy().copy())
+    return wall, rcs, commits, q_stats
+
+
+def loop_host_backoff(eng, alg, fresh, E, rq, timed):
+    """Path B with the reference queue (tests/abortq_ref.py) on the host."""
+    F = fresh[0].n_txn
+    rq.clear()
+    h = fresh[0]
+    h_src, h_cnt = np.arange(F, dtype=np.uint32), np.zeros(F, np.uint32)
+    cur, held = h.to_torch(DEV), None
+    wall, rcs, commits = [], [], 0
+    for e in range(E):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc, st = decide(eng, alg, cur, held)
+        commits += st["n_commit"]
+        hrc = rc.cpu().numpy()
+        if e + 1 < E:
+            nf = fresh[e + 1]
+            if alg == "nowait":
+                ok = np.repeat(hrc == RC_RCOK, np.diff(h.offsets.astype(np.int64)))
+                held = (torch.from_numpy(h.keys[ok].view(np.int64)).to(DEV), torch.from_numpy(h.acctype[ok]).to(DEV))
+            code, _, _ = rq.push(h, hrc, RC_ABORT, h_src, h_cnt, e)
+            assert code == 0
+            _, n0, m0, r = rq.pop(e + 1)
+            h = d.EpochBatch(np.concatenate([r["offsets"], nf.offsets[1:] + np.uint32(m0)]).astype(np.uint32),
+                             np.concatenate([r["keys"], nf.keys]), np.concatenate([r["acctype"], nf.acctype]))
+            h_src = np.concatenate([r["src"], np.arange((e + 1) * F, (e + 2) * F, dtype=np.uint32)])
+            h_cnt = np.concatenate([r["cnt"], np.zeros(F, np.uint32)])
+            cur = h.to_torch(DEV)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        if not timed:
+            rcs.append(hrc.copy())
+    return wall, rcs, commits
+
+
+def closed_loop_backoff(eng, a):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import abortq_ref
+    E, F = a.epochs, a.fresh
+    policy = {"none": _abi.BACKOFF_NONE, "reference": _abi.BACKOFF_REFERENCE, "exp": _abi.BACKOFF_EXP}[a.backoff]
+    fresh = [d.gen_ycsb(n_txn=F, zipf_theta=a.theta, seed=1000 + e) for e in range(E)]
+    fresh_dev = [dev_batch(b) for b in fresh]
+    cap_n, cap_m = E * F, sum(b.nnz for b in fresh)
+    eng.reserve(cap_n, cap_m)
+    bufs = [d.EpochBatch(torch.empty(cap_n + 1, dtype=torch.int32, device=DEV),
+                         torch.empty(cap_m, dtype=torch.int64, device=DEV),
+                         torch.empty(cap_m, dtype=torch.uint8, device=DEV),
+                         meta={"src": torch.empty(cap_n, dtype=torch.int32, device=DEV),
+                               "cnt": torch.empty(cap_n, dtype=torch.int32, device=DEV)}) for _ in range(2)]
+    q = eng.abort_queue(cap_n, cap_m, a.penalty, a.penalty_max, policy)
+    rq = abortq_ref.AbortQueue(cap_n, cap_m, a.penalty, a.penalty_max, policy)
+    _, rc_a, _, _ = loop_device_backoff(eng, a.alg, fresh_dev, E, bufs, q, timed=False)
+    _, rc_b, _ = loop_host_backoff(eng, a.alg, fresh, E, rq, timed=False)
+    same = len(rc_a) == len(rc_b) and all(np.array_equal(x, y) for x, y in zip(rc_a, rc_b))
+    for _ in range(max(a.loop_warmup - 1, 0)):
+        loop_device_backoff(eng, a.alg, fresh_dev, E, bufs, q, timed=True)
+        loop_host_backoff(eng, a.alg, fresh, E, rq, timed=True)
+    wa, wb, ca, cb, qst = [], [], 0, 0, []
+    for _ in range(a.loop_reps):  # alternately
+        w, _, c, s = loop_device_backoff(eng, a.alg, fresh_dev, E, bufs, q, timed=True)
+        wa += w
+        ca += c
+        qst += s
+        w, _, c = loop_host_backoff(eng, a.alg, fresh, E, rq, timed=True)
+        wb += w
+        cb += c
+    left = q.size()
+    q.close()
+    res = {"alg": a.alg, "epochs": E, "fresh": F, "theta": a.theta, "backoff": a.backoff, "penalty": a.penalty,
+           "penalty_max": a.penalty_max, "rc_identical": bool(same),
+           "txns_per_epoch": [int(r.size) for r in rc_a],
+           "commits_per_epoch": [int((r == RC_RCOK).sum()) for r in rc_a],
+           "parked_at_end": left,
+           "A_queue": {"wall_ms_per_epoch": mmm(wa), "goodput_commits_per_s": ca / (sum(wa) * 1e-3),
+                       "push_device_ms": mmm([s[0]["device_ms"] for s in qst]),
+                       "pop_device_ms": mmm([s[1]["device_ms"] for s in qst])},
+           "B_host": {"wall_ms_per_epoch": mmm(wb), "goodput_commits_per_s": cb / (sum(wb) * 1e-3)}}
+    res["wall_B_over_A"] = res["B_host"]["wall_ms_per_epoch"]["median"] / res["A_queue"]["wall_ms_per_epoch"]["median"]
+    res["goodput_A_over_B"] = res["A_queue"]["goodput_commits_per_s"] / res["B_host"]["goodput_commits_per_s"]
+    print(f"closed loop {a.alg}, back-off {a.backoff} (penalty {a.penalty}, max {a.penalty_max}): {E} epochs of "
+          f"{F} fresh txns, theta {a.theta}; txns per epoch {res['txns_per_epoch']}, commits "
+          f"{res['commits_per_epoch']}, parked at the end {left}")
+    for k in ("A_queue", "B_host"):
+        r = res[k]
+        print(f"  {k:9s} wall ms/epoch {fmt(r['wall_ms_per_epoch'])}  goodput {r['goodput_commits_per_s'] / 1e6:.2f} M commits/s"
+              + (f"  push device_ms {fmt(r['push_device_ms'])}  pop device_ms {fmt(r['pop_device_ms'])}"
+                 if "push_device_ms" in r else ""))
+    print(f"  wall B / A = {res['wall_B_over_A']:.2f}  goodput A / B = {res['goodput_A_over_B']:.2f}  "
+          f"rc identical {res['rc_identical']}")
+    return res
+
+
 def closed_loop(eng, a):
     E, F = a.epochs, a.fresh
     fresh = [d.gen_ycsb(n_txn=F, zipf_theta=a.theta, seed=1000 + e) for e in range(E)]
@@ -228,6 +436,10 @@ def main():
     ap.add_argument("--select-shapes", choices=("both", "c2", "headline", "none"), default="both")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--backoff", choices=("none", "reference", "exp"), default=None)
+    ap.add_argument("--penalty", type=int, default=1)
+    ap.add_argument("--penalty-max", type=int, default=4)
+    ap.add_argument("--queue-shapes", choices=("both", "c2", "headline", "none"), default="none")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "retry_loop needs cuda:0"
@@ -237,9 +449,12 @@ def main():
             if a.select_shapes in ("both", key):
                 print(f"select alone, {name}:")
                 out[f"select {name}"] = time_select(eng, n, a)
+            if a.queue_shapes in ("both", key):
+                print(f"abort queue alone, {name}:")
+                out[f"queue {name}"] = time_queue(eng, n, a)
     with d.Engine(0) as eng:
         if a.epochs > 0:
-            out["closed_loop"] = closed_loop(eng, a)
+            out["closed_loop"] = closed_loop_backoff(eng, a) if a.backoff else closed_loop(eng, a)
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
