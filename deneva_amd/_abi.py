@@ -43,6 +43,7 @@ UNIQUE_ID_BYTES = 128
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64)
 BACKOFF_REFERENCE, BACKOFF_NONE, BACKOFF_EXP = 0, 1, 2  # dcc_abortq_params.policy
 ABORTQ_SORT_FULL = 0x1
+LOCK_EX, LOCK_SH = 0, 1  # lock_t, system/global.h:289 (dcc_locktab_export)
 OPT_RECHECK = 1
 OPT_BATCH_MAX = 2
 OPT_SOLVER = 5
@@ -112,6 +113,11 @@ class AbortqParams(C.Structure):
         ("policy", C.c_uint32),
         ("flags", C.c_uint32),
     ]
+
+
+class LocktabParams(C.Structure):
+    """dcc_locktab_params: room of a lock table."""
+    _fields_ = [("cap_rows", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -280,6 +286,19 @@ _SIGS = [
     ("dcc_abortq_clear", C.c_int, [_P]),
     ("dcc_abortq_push_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
     ("dcc_abortq_pop_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    ("dcc_locktab_create", C.c_int, [_P, C.POINTER(LocktabParams), C.POINTER(C.c_void_p)]),
+    ("dcc_locktab_destroy", None, [_P]),
+    ("dcc_locktab_lock_epoch", C.c_int, [_P, C.POINTER(Batch), _P, _P, C.POINTER(Stats)]),
+    ("dcc_locktab_release", C.c_int,
+     [_P, C.POINTER(Batch), _P, C.c_uint8, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    ("dcc_locktab_acquire_rows", C.c_int, [_P, C.POINTER(CalvinHeld), C.c_uint32]),
+    ("dcc_locktab_release_rows", C.c_int, [_P, _P, C.c_uint64, C.c_uint32]),
+    ("dcc_locktab_export", C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("dcc_locktab_size", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("dcc_locktab_clear", C.c_int, [_P]),
+    ("dcc_locktab_pass_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("dcc_locktab_epoch_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]),
+    ("dcc_locktab_release_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64]),
     ("dcc_ycsb_params_default", None, [C.POINTER(YcsbParams)]),
     ("dcc_gen_ycsb", C.c_int, [C.POINTER(YcsbParams), _P, _P, _P, _P]),
     ("dcc_tpcc_params_default", None, [C.POINTER(TpccParams)]),

@@ -17,6 +17,7 @@
 
 namespace dcc {
 struct SwShard;  // occ_kernels.h: one key-sharded sweep level's serial range
+struct Slot;     // dcc_device.h: one slot of the per-epoch hash table
 }
 
 struct dcc_ctx;
@@ -130,6 +131,42 @@ struct dcc_abortq {
   uint64_t seq = 0;         // txns pushed over the queue's life
   uint64_t due_lo = ~0ull;  // a lower bound of every parked due: the smallest `now` pushed
                             // with since the queue was last empty
+};
+
+// The NO_WAIT lock table that lives across epochs (locktab.hip): Row_lock's
+// (lock_type, owner_cnt) per row in an open-addressing table of n_slots
+// 16-byte slots.  A released row keeps its slot, so the host tracks the slots
+// in use next to the rows held and rebuilds into the other buffer when an
+// epoch's requests would push the table past half full.
+struct dcc_locktab {
+  dcc_ctx* owner = nullptr;  // the creating context (a multi-GPU one runs the work on rank 0)
+  dcc_locktab_params P{};
+  DevBuf tab[2];                    // the table and the rebuild's target
+  DevBuf ctl;                       // control words
+  DevBuf st_keys, st_type, st_cnt;  // the outputs of a host export
+  DevBuf st_rc;                     // rc of a host release
+  int cur = 0;
+  uint64_t n_slots = 0;
+  uint64_t slots_used = 0;  // keys in the current buffer
+  uint64_t rows_held = 0;   // rows with owner_cnt > 0
+  uint64_t holds = 0;       // the sum of all owner_cnt
+  uint64_t rebuilds = 0;
+  double pass_ms[3] = {};   // seed / grant / rebuild of the last profiled epoch or acquire
+  bool rebuilt = false;     // the call in flight rebuilt (pev[7] .. pev[0] is its time)
+};
+
+// What the table's passes of a lock epoch read of it (nowait.hip fills it in).
+struct LtEpoch {
+  uint64_t n = 0;
+  const uint32_t* off = nullptr;
+  const uint64_t* keys = nullptr;
+  const uint8_t* at = nullptr;
+  const uint32_t* sid = nullptr;   // per-epoch slot id of every request
+  const uint8_t* state = nullptr;  // decided state bytes
+  dcc::Slot* tab = nullptr;        // the per-epoch table
+  uint32_t lp = 0;                 // log2 lanes per txn
+  const uint32_t* err = nullptr;   // the epoch's error word
+  unsigned grid = 1;
 };
 
 struct dcc_ctx {
@@ -399,8 +436,27 @@ struct dcc_ctx {
                    uint8_t* out_rc, uint32_t* out_wave, dcc_stats* st);
   // NO_WAIT 2PL (nowait.hip)
   int nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
+  // lt: the epoch runs against this lock table and leaves its grants in it
   int nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
-                   uint32_t* out_conflict, dcc_stats* st);
+                   uint32_t* out_conflict, dcc_stats* st, dcc_locktab* lt = nullptr);
+  // lock table (locktab.hip): the calls on the context that runs them.  An
+  // epoch calls begin (room for `incoming` requests, rebuilding if needed;
+  // control words cleared), seed after the per-epoch table is built, grant
+  // after the decisions (it enqueues the read-back too) and, after the
+  // epoch's last synchronisation found no error, end (the host state follows)
+  static constexpr size_t LT_HMISC_OFF = 1024;  // the table's control words in hmisc
+  int locktab_alloc(dcc_locktab* lt);
+  int locktab_begin(dcc_locktab* lt, uint64_t incoming, const char* what);
+  int locktab_seed(dcc_locktab* lt, const LtEpoch& E);
+  int locktab_grant(dcc_locktab* lt, const LtEpoch& E);
+  int locktab_end(dcc_locktab* lt, uint64_t* granted);
+  int locktab_release(dcc_locktab* lt, const dcc_batch* b, const uint8_t* rc_in, uint8_t want,
+                      const uint64_t* keys, uint64_t n_keys, bool keys_dev, uint64_t* out_n,
+                      uint64_t* out_nnz, dcc_stats* st);
+  int locktab_acquire(dcc_locktab* lt, const dcc_calvin_held* rows, bool dev);
+  int locktab_export(dcc_locktab* lt, uint64_t* keys, uint8_t* lock_type, uint32_t* owner_cnt,
+                     uint64_t cap, bool dev, uint64_t* out_n);
+  int locktab_clear(dcc_locktab* lt);
   // select by decision into a CSR (select.hip)
   int select_reserve(uint64_t n, uint64_t nnz);
   int select_batch(const dcc_batch* b, const uint8_t* rc_in, uint8_t want, const uint32_t* src_in,
@@ -416,6 +472,8 @@ struct dcc_ctx {
   DevBuf sh_off, sh_keys, sh_at, sh_src, sh_cnt, sh_bsum, sh_rc, sh_tn, sh_grp;
   int shard_stage(const dcc_batch* b, uint32_t rank, uint32_t R, dcc_batch& sb, DevBatch* full_out = nullptr);
   int shard_groups(const uint32_t* grp, uint64_t m, uint32_t* out_dev);  // groups to batch order
+  // lock tables created on this context and not yet destroyed (freed with it)
+  std::vector<std::unique_ptr<dcc_locktab>> locktabs;
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes

@@ -147,7 +147,8 @@ extern "C" int dcc_init(dcc_ctx** out, int device_id) {
 extern "C" void dcc_destroy(dcc_ctx* ctx) {
   if (!ctx) return;
   dcc_pipe_destroy(ctx);
-  ctx->abortqs.clear();  // abort queues still alive (every call on them has synchronised)
+  ctx->abortqs.clear();   // abort queues still alive (every call on them has synchronised)
+  ctx->locktabs.clear();  // lock tables, likewise
   dcc_multi_destroy(ctx);
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);

@@ -44,38 +44,19 @@
 #include "dcc.h"
 #include "dcc_ctx.h"
 #include "dcc_device.h"
+#include "nowait_lanes.h"
 #include "occ_kernels.h"
 
 using namespace dcc;
 
 namespace {
 
-constexpr uint32_t NW_T = 256;        // threads per workgroup
 constexpr uint32_t NW_RING = 64;      // list-length ring (> the rounds of one host batch)
 constexpr uint32_t NW_STAGE = 1024;   // blocked txns a workgroup stages before one list append
 constexpr uint32_t NW_ERR_OFF = 1, NW_ERR_KEY = 2, NW_ERR_FULL = 4, NW_ERR_STATE = 8;
 // counter words (nw_misc)
 constexpr uint32_t NW_C_ERR = 0, NW_C_MAXLEN = 1, NW_C_NEX = 2, NW_C_RO = 3, NW_C_COMMIT = 4,
                    NW_C_RING = 8, NW_C_WORDS = NW_C_RING + NW_RING;
-
-__device__ inline uint32_t is_ex(uint8_t t) { return (t == DCC_RD || t == DCC_SCAN) ? 0u : 1u; }
-
-// The P = 2^lp lanes of a txn inside the wave.
-struct Seg {
-  uint32_t a;     // access ordinal of this lane
-  uint32_t gl;    // txn of this lane within the workgroup's step
-  uint32_t seg0;  // first lane of the txn
-  uint64_t mask;  // the txn's lanes
-};
-__device__ inline Seg seg_of(uint32_t lp) {
-  const uint32_t P = 1u << lp;
-  Seg s;
-  s.a = threadIdx.x & (P - 1);
-  s.gl = threadIdx.x >> lp;
-  s.seg0 = lane_id() & ~(P - 1);
-  s.mask = (P == 64 ? ~0ull : ((1ull << P) - 1ull)) << s.seg0;
-  return s;
-}
 
 // A txn names a row twice with EX on either side (NO_WAIT keeps no owner
 // list, row_lock.cpp:176-182): the lanes of the later requests.  Rows compare
@@ -385,7 +366,7 @@ int dcc_ctx::nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict) {
 }
 
 int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
-                          uint32_t* out_conflict, dcc_stats* st) {
+                          uint32_t* out_conflict, dcc_stats* st, dcc_locktab* lt) {
   dcc_ctx* ctx = this;
   EpochStats es;
   dcc_stats& S = es.S;
@@ -393,6 +374,7 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   CR(check_batch(b, false));  // the offsets are checked on the device (k_nw_check)
   if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "nowait: single-GPU engine");
   const uint64_t hn = held ? held->n : 0;
+  if (lt && hn) return fail(DCC_EINVAL, "nowait: a held list next to a lock table");
   if (hn && (!held->keys || !held->acctype)) return fail(DCC_EINVAL, "nowait: null held keys/acctype");
   const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
   if (b->n_txn == 0) {
@@ -438,6 +420,7 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   const bool prof = profiling;
   CK(hipEventRecord(ev0, stream));
   if (prof) CK(hipEventRecord(pev[0], stream));
+  if (lt) CR(locktab_begin(lt, m, "lock epoch"));  // room for every request, or DCC_ERANGE
   Slot* tab = (Slot*)table.p;
   CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
   if (hn) {
@@ -449,6 +432,21 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   NwArgs A{n, d.off, d.keys, d.acctype, tab, mask, lp, (uint32_t*)nw_sid.p, (uint8_t*)state.p, cnt};
   k_nw_build<<<nw_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
   CK(hipGetLastError());
+  // the table's held rows take the place of a held list: their tag-0 words
+  LtEpoch L;
+  if (lt) {
+    L.n = n;
+    L.off = d.off;
+    L.keys = d.keys;
+    L.at = d.acctype;
+    L.sid = A.sid;
+    L.state = A.state;
+    L.tab = tab;
+    L.lp = lp;
+    L.err = &cnt[NW_C_ERR];
+    L.grid = nw_grid(n, per_block, max_grid);
+    CR(locktab_seed(lt, L));
+  }
   if (prof) CK(hipEventRecord(pev[1], stream));
 
   // ---- rounds: decide(r) reads its list length from ring[r % NW_RING] and
@@ -495,6 +493,7 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   if (prof) CK(hipEventRecord(pev[3], stream));
   k_nw_final<<<nw_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
   CK(hipGetLastError());
+  if (lt) CR(locktab_grant(lt, L));  // the committed txns' requests stay in the table
   if (prof) CK(hipEventRecord(pev[4], stream));
   CK(hipEventRecord(ev1, stream));
   if (!dev) {
@@ -513,6 +512,11 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   S.nnz_w = hc[NW_C_NEX];
   S.n_readonly = hc[NW_C_RO];
   S.alg_bytes = dcc_nowait_alg_bytes(n, m, out_conflict != nullptr);
+  if (lt) {
+    uint64_t granted = 0;
+    CR(locktab_end(lt, &granted));
+    S.alg_bytes = dcc_locktab_epoch_alg_bytes(n, m, granted, out_conflict != nullptr);
+  }
   CR(es.finish(this, 4));
   if (st) *st = S;
   return DCC_OK;

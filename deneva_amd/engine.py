@@ -142,7 +142,7 @@ class Engine:
     def close(self) -> None:
         if getattr(self, "_h", None):
             for q in list(getattr(self, "_queues", [])):
-                q._q = None  # dcc_destroy frees the queues still alive
+                q._q = None  # dcc_destroy frees the queues and lock tables still alive
             self._queues = []
             lib.dcc_destroy(self._h)
             self._h = None
@@ -577,6 +577,12 @@ class Engine:
         system/abort_queue.cpp on the caller's clock."""
         return AbortQueue(self, cap_txn, cap_nnz, penalty, penalty_max, policy, flags)
 
+    # ------------------------------ NO_WAIT lock table that lives across epochs
+    def locktab(self, cap_rows: int) -> "LockTable":
+        """A device-resident NO_WAIT lock table with room for cap_rows rows
+        (dcc_locktab_create): Row_lock's lock_type / owner_cnt across epochs."""
+        return LockTable(self, cap_rows)
+
     def held_from(self, batch: EpochBatch, rc):
         """The requests of the txns that committed (rc == RC_RCOK) as (keys,
         acctype): the held prefix that nowait_lock_epoch(held=...) and
@@ -813,6 +819,142 @@ class AbortQueue:
         _check(lib.dcc_abortq_clear(self._handle()), self._eng._h)
 
 
+class LockTable:
+    """dcc_locktab: the NO_WAIT lock state in device memory, acquired into by
+    epochs and released from by finished txns (Engine.locktab)."""
+
+    def __init__(self, eng: "Engine", cap_rows: int):
+        self._eng = eng
+        self._q = None
+        self.cap_rows = int(cap_rows)
+        p = _abi.LocktabParams(cap_rows, 0, 0)
+        h = C.c_void_p()
+        _check(lib.dcc_locktab_create(eng._h, C.byref(p), C.byref(h)), eng._h)
+        self._q = h
+        eng._queues.append(self)
+
+    def close(self) -> None:
+        if self._q is not None:
+            lib.dcc_locktab_destroy(self._q)
+            self._q = None
+            if self in self._eng._queues:
+                self._eng._queues.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if self._q is None:
+            raise ValueError("lock table is closed")
+        return self._q
+
+    def lock_epoch(self, batch: EpochBatch, want_conflict: bool = True, out_rc=None, out_conflict=None):
+        """The epoch against the table's rows; the requests of its committed
+        txns stay in the table (dcc_locktab_lock_epoch).  Returns (rc u8[n],
+        conflict u32[n] | None, stats) as Engine.nowait_lock_epoch."""
+        n = batch.n_txn
+        if batch.on_device:
+            import torch
+            dv = batch.offsets.device
+            if out_rc is None:
+                out_rc = torch.empty(max(n, 1), dtype=torch.uint8, device=dv)
+            if want_conflict and out_conflict is None:
+                out_conflict = torch.empty(max(n, 1), dtype=torch.int32, device=dv)
+        else:
+            if out_rc is None:
+                out_rc = np.empty(max(n, 1), np.uint8)
+            if want_conflict and out_conflict is None:
+                out_conflict = np.empty(max(n, 1), np.uint32)
+        if not want_conflict:
+            out_conflict = None
+        if out_rc.shape[0] < n or (out_conflict is not None and out_conflict.shape[0] < n):
+            raise ValueError("lock_epoch: output buffer shorter than the epoch")
+        st = _abi.Stats()
+        b = batch.to_c()
+        _check(lib.dcc_locktab_lock_epoch(self._handle(), C.byref(b), _ptr(out_rc), _ptr(out_conflict),
+                                          C.byref(st)), self._eng._h)
+        return out_rc[:n], (out_conflict[:n] if want_conflict else None), st.as_dict()
+
+    def release(self, batch: EpochBatch, rc=None, want: int = _abi.RC_RCOK):
+        """lock_release for every access of the txns with rc[i] == want (rc
+        None: of every txn) (dcc_locktab_release): returns (n, nnz, stats) of
+        what was released.  A row released more often than it is held raises
+        DccError(DCC_EINVAL) and leaves the table unchanged."""
+        if rc is not None:
+            if not batch.on_device:
+                rc = np.ascontiguousarray(rc, np.uint8)
+            if rc.shape[0] < batch.n_txn:
+                raise ValueError("release: rc shorter than the epoch")
+        st = _abi.Stats()
+        b = batch.to_c()
+        ns, ms = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.dcc_locktab_release(self._handle(), C.byref(b), _ptr(rc), want, C.byref(ns), C.byref(ms),
+                                       C.byref(st)), self._eng._h)
+        return int(ns.value), int(ms.value), st.as_dict()
+
+    def acquire_rows(self, keys, acctype) -> None:
+        """Take a plain (key, access type) list as a held prefix is taken: a
+        row is EX if any of its entries is EX, its count goes up by one per
+        entry (dcc_locktab_acquire_rows)."""
+        dev = _is_device(keys)
+        if not dev:
+            keys = np.ascontiguousarray(keys, np.uint64)
+            acctype = np.ascontiguousarray(acctype, np.uint8)
+        if int(acctype.shape[0]) != int(keys.shape[0]) or _itemsize(keys) != 8 or _itemsize(acctype) != 1:
+            raise ValueError("acquire_rows: u64 keys and u8 access types of one length")
+        h = _abi.CalvinHeld(int(keys.shape[0]), _ptr(keys), _ptr(acctype))
+        _check(lib.dcc_locktab_acquire_rows(self._handle(), C.byref(h), _abi.DEVICE_PTRS if dev else 0),
+               self._eng._h)
+
+    def release_rows(self, keys) -> None:
+        """lock_release once per entry of a plain key list (dcc_locktab_release_rows)."""
+        dev = _is_device(keys)
+        if not dev:
+            keys = np.ascontiguousarray(keys, np.uint64)
+        if _itemsize(keys) != 8:
+            raise TypeError("release_rows: u64 keys")
+        _check(lib.dcc_locktab_release_rows(self._handle(), _ptr(keys), int(keys.shape[0]),
+                                            _abi.DEVICE_PTRS if dev else 0), self._eng._h)
+
+    def export(self, device=None):
+        """(keys u64, lock_type u8, owner_cnt u32) of the rows with owner_cnt >
+        0, in any order (dcc_locktab_export); lock_type is LOCK_EX / LOCK_SH.
+        numpy arrays, or torch tensors on `device` when given."""
+        rows = self.size()[0]
+        n = C.c_uint64(0)
+        if device is not None:
+            import torch
+            k = torch.empty(max(rows, 1), dtype=torch.int64, device=device)
+            t = torch.empty(max(rows, 1), dtype=torch.uint8, device=device)
+            c = torch.empty(max(rows, 1), dtype=torch.int32, device=device)
+        else:
+            k, t, c = np.empty(max(rows, 1), np.uint64), np.empty(max(rows, 1), np.uint8), \
+                np.empty(max(rows, 1), np.uint32)
+        _check(lib.dcc_locktab_export(self._handle(), _ptr(k), _ptr(t), _ptr(c), rows,
+                                      _abi.DEVICE_PTRS if device is not None else 0, C.byref(n)), self._eng._h)
+        m = int(n.value)
+        return k[:m], t[:m], c[:m]
+
+    def size(self):
+        """(rows held, slots in use, rebuilds): host state, no device work."""
+        r, s, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib.dcc_locktab_size(self._handle(), C.byref(r), C.byref(s), C.byref(b)), self._eng._h)
+        return int(r.value), int(s.value), int(b.value)
+
+    def pass_ms(self):
+        """{"seed", "grant", "rebuild"}: device ms of the table's own passes in
+        the last profiled lock epoch or acquire (dcc_locktab_pass_ms)."""
+        out = (C.c_double * 3)()
+        _check(lib.dcc_locktab_pass_ms(self._handle(), out), self._eng._h)
+        return {"seed": out[0], "grant": out[1], "rebuild": out[2]}
+
+    def clear(self) -> None:
+        _check(lib.dcc_locktab_clear(self._handle()), self._eng._h)
+
+
 def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(_abi.UNIQUE_ID_BYTES)
     _check(lib.dcc_comm_unique_id(buf))
@@ -868,6 +1010,14 @@ def abortq_push_alg_bytes(n_txn: int, n_sel: int, nnz_sel: int) -> int:
 
 def abortq_pop_alg_bytes(n_q: int, nnz_q: int, n_due: int, nnz_due: int) -> int:
     return int(lib.dcc_abortq_pop_alg_bytes(n_q, nnz_q, n_due, nnz_due))
+
+
+def locktab_epoch_alg_bytes(n_txn: int, nnz: int, nnz_granted: int, with_conflict: bool = True) -> int:
+    return int(lib.dcc_locktab_epoch_alg_bytes(n_txn, nnz, nnz_granted, int(with_conflict)))
+
+
+def locktab_release_alg_bytes(n_txn: int, n_sel: int, nnz_sel: int) -> int:
+    return int(lib.dcc_locktab_release_alg_bytes(n_txn, n_sel, nnz_sel))
 
 
 def ycsb_params(**kw) -> _abi.YcsbParams:

@@ -477,6 +477,109 @@ int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const dcc_calvin
  * + 16 nnz (one lock-table slot per request) + N (RC) [+ 4N conflict]. */
 uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
 
+/* ------------------------------ NO_WAIT lock table that lives across epochs */
+/* Row_lock's NO_WAIT state where the batches live: a device-resident map
+ * row -> (lock_type, owner_cnt) that epochs acquire into and finished txns
+ * release from, for the life of the handle.  A row that is absent or has
+ * owner_cnt == 0 is LOCK_NONE.
+ *
+ * dcc_locktab_lock_epoch: the epoch's txns run get_row in index order and list
+ * order against the table's current state, exactly as dcc_nowait_lock_epoch
+ * defines it (self-conflicts included) with the table's rows as its held
+ * prefix: a row with owner_cnt > 0 is held, EX-held iff lock_type == LOCK_EX.
+ * out_rc, out_conflict and the stats are those of that call, alg_bytes being
+ * dcc_locktab_epoch_alg_bytes.  Aborted txns leave no trace; every request of
+ * a committed txn stays in the table: owner_cnt++, lock_type = its type
+ * (row_lock.cpp:190-194), so a txn naming a row twice with SH adds 2.  A failed
+ * epoch (malformed offsets, reserved key, a txn above MAX_ROW_PER_TXN, no
+ * room) leaves the table unchanged.
+ *
+ * dcc_locktab_release: every access of every txn with rc[i] == want (rc NULL:
+ * of every txn) does lock_release (row_lock.cpp:240-256): owner_cnt--, and
+ * lock_type = LOCK_NONE at zero.  NO_WAIT keeps no owner list, so the access
+ * type plays no part.  The reference's assert(owner_cnt > 0) is an error here:
+ * if the releases of ONE CALL together name a row more often than it is held,
+ * or name a row the table does not have, the call returns DCC_EINVAL and the
+ * table is unchanged (two txns of one call each releasing a row held once
+ * fail, although each alone would pass).  Malformed offsets give DCC_EINVAL.
+ * Txn length is unbounded.  *out_n / *out_nnz (host memory, may be NULL) are
+ * the released txns / accesses.  Stats: n_commit = released txns, n_abort =
+ * the others, alg_bytes (dcc_locktab_release_alg_bytes), device_ms, total_ms;
+ * with profiling phase_ms: 0 = offsets check, 1 = scratch add, 2 = compare,
+ * 3 = apply.
+ *
+ * dcc_locktab_acquire_rows takes a plain (key, access type) list as the held
+ * prefix of dcc_nowait_lock_epoch does: a row is EX if any of its entries is
+ * EX, and its count goes up by one per entry.  dcc_locktab_release_rows
+ * releases a plain key list under the rule of dcc_locktab_release.
+ * dcc_locktab_export writes (key, lock_type, owner_cnt) of the rows with
+ * owner_cnt > 0, in any order; lock_type is the reference's lock_t
+ * (DCC_LOCK_EX / DCC_LOCK_SH); each output may be NULL; *out_n = the rows
+ * held; cap smaller than that is DCC_ERANGE with nothing written.
+ * `flags`: DCC_DEVICE_PTRS when the arrays of that call are device memory.
+ *
+ * Room: the table has 2^k slots, the smallest power of two >= 2 cap_rows, and
+ * at most cap_rows of them are ever in use (the load bound: at most half
+ * full).  A released row keeps its slot at count 0, so slots fill up with
+ * rows that were held once.  Before a lock epoch or an acquire the slots in
+ * use plus the incoming requests (an upper bound on the new rows) must fit
+ * cap_rows; if they do not, the held rows are first re-inserted into the
+ * second table buffer (a rebuild: slots in use = rows held afterwards); if
+ * rows held + incoming requests still exceed cap_rows the call returns
+ * DCC_ERANGE and the table is logically unchanged.  owner_cnt is a 31-bit count next to the
+ * EX bit: the sum of all counts is kept below 2^31 (DCC_ERANGE otherwise).
+ *
+ * With DCC_DEVICE_PTRS in batch->flags the batch, rc and the outputs are
+ * device memory; compact batch forms are accepted.  The table is created with
+ * its capacity, lives on the context's GPU (rank 0's of a dcc_init_multi
+ * context) and is freed by dcc_destroy if still alive.  A lock epoch under a
+ * communicator of more than one rank is DCC_ENOTSUP.  No call is a
+ * collective.  Pipelined OCC epochs in flight complete first.  Both table
+ * buffers, the control words and the staging of host exports are allocated
+ * at create, the per-epoch workspaces by dcc_reserve: a warmed-up call on a
+ * device batch allocates nothing.  dcc_nowait_lock_epoch and its `held`
+ * argument are independent of any table. */
+#define DCC_LOCK_EX 0 /* lock_t, system/global.h:289 */
+#define DCC_LOCK_SH 1
+typedef struct dcc_locktab dcc_locktab;
+typedef struct dcc_locktab_params {
+  uint64_t cap_rows; /* rows (held or once held) the table has room for; 2^k <= 2^30 slots */
+  uint32_t flags;    /* 0 */
+  uint32_t reserved;
+} dcc_locktab_params;
+int dcc_locktab_create(dcc_ctx* ctx, const dcc_locktab_params* params, dcc_locktab** out);
+void dcc_locktab_destroy(dcc_locktab* lt);
+int dcc_locktab_lock_epoch(dcc_locktab* lt, const dcc_batch* batch, uint8_t* out_rc,
+                           uint32_t* out_conflict, dcc_stats* out_stats);
+int dcc_locktab_release(dcc_locktab* lt, const dcc_batch* batch, const uint8_t* rc, uint8_t want,
+                        uint64_t* out_n, uint64_t* out_nnz, dcc_stats* out_stats);
+int dcc_locktab_acquire_rows(dcc_locktab* lt, const dcc_calvin_held* rows, uint32_t flags);
+int dcc_locktab_release_rows(dcc_locktab* lt, const uint64_t* keys, uint64_t n, uint32_t flags);
+int dcc_locktab_export(dcc_locktab* lt, uint64_t* keys, uint8_t* lock_type, uint32_t* owner_cnt,
+                       uint64_t cap, uint32_t flags, uint64_t* out_n);
+/* Rows held, slots in use (rows held or once held since the last rebuild or
+ * clear), rebuilds over the table's life: host state, no device work.  Each
+ * may be NULL. */
+int dcc_locktab_size(const dcc_locktab* lt, uint64_t* rows_held, uint64_t* slots_used,
+                     uint64_t* rebuilds);
+/* Drop every row (the buffers stay). */
+int dcc_locktab_clear(dcc_locktab* lt);
+/* Device times of the table's own passes in the last lock epoch or acquire
+ * run with profiling on: out_ms[0] = seed pass, [1] = grant pass, [2] = the
+ * rebuild (0 when there was none). */
+int dcc_locktab_pass_ms(const dcc_locktab* lt, double out_ms[3]);
+/* Algorithmic bytes of a table epoch: the NO_WAIT epoch's
+ * (dcc_nowait_alg_bytes) + 16 nnz (seed: one table slot probed per request)
+ * + N (grant: the decision byte) + 25 nnz_granted (grant: key and type read
+ * again, one table slot updated). */
+uint64_t dcc_locktab_epoch_alg_bytes(uint64_t n_txn, uint64_t nnz, uint64_t nnz_granted,
+                                     int with_conflict);
+/* Algorithmic bytes of a release of n_sel txns / nnz_sel accesses out of
+ * n_txn: 4(N+1) offsets + N (RC) + per released access the key (8), its slot
+ * id written and read twice (12) and its table slot touched by each of the
+ * three passes (48). */
+uint64_t dcc_locktab_release_alg_bytes(uint64_t n_txn, uint64_t n_sel, uint64_t nnz_sel);
+
 /* ------------------------------------------- select by decision (carry) */
 /* The next epoch from this one's decisions, where the batch lives: the txns
  * with rc[i] == want (exact equality against any byte value: DCC_RC_ABORT for

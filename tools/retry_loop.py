@@ -7,6 +7,7 @@ goodput: commits per second with the retries in the loop.
                                [--select-shapes both|c2|headline|none] [--warmup 5] [--steps 20]
                                [--backoff none|reference|exp --penalty P --penalty-max M]
                                [--queue-shapes both|c2|headline|none] [--json PATH]
+                               [--hold D] [--table-shapes both|c2|headline|none]
 
 The loop runs twice in one process on the same pre-generated fresh txns
 (gen_ycsb, already on the device, so the loop times the engine and the carry,
@@ -35,7 +36,21 @@ and carries the epoch's src / cnt arrays on the device, the fresh txns getting
 the push of the aborted txns next to dcc_batch_select of the same selection
 and dcc_copy_bandwidth over the same bytes, a pop that releases all of them
 and one that releases about half (EXP, cnt 0 or 1 at random), the pop's
-phases, and the pop of all with the sort over all 64 bits."""
+phases, and the pop of all with the sort over all 64 bits.
+
+--hold D (--alg nowait): the committed txns of epoch e keep their rows until
+epoch e + D, as the reference's do while they execute.  Path A keeps the lock
+state in a device lock table (Engine.locktab): lock_epoch, then
+release(batch of epoch e - D, its rc, RCOK).  Path B is the way without one,
+on the device: dcc_batch_select(RCOK) of each of the last D epochs, chained
+through txn_base / nnz_base into one held list that is passed to
+dcc_nowait_lock_epoch.  Both carry the aborted txns with dcc_batch_select.
+
+--table-shapes times the table epoch against dcc_nowait_lock_epoch with the
+equivalent held list, alternately, on the C2 and the headline epoch with the
+commits of the previous one and of the previous four epochs held; the release
+alone next to dcc_copy_bandwidth over its byte count; and the seed / grant /
+rebuild passes and the release's phases from profiled calls."""
 import argparse
 import ctypes as C
 import json
@@ -178,6 +193,91 @@ def time_queue(eng, n, a):
           f"{fmt(r['pop_all_sort64']['device_ms'])}")
     for k, v in r["phase_ms"].items():
         print(f"    phases {k}: {({nm: round(x, 4) for nm, x in v.items()})}")
+    return r
+
+
+# ------------------------------------------------------------- table alone
+def time_table(eng, n, K, a):
+    """Epoch K against the commits of epochs 0 .. K-1: in a lock table, and as
+    a held list."""
+    bs = [d.gen_ycsb(n_txn=n, zipf_theta=0.9, seed=2000 + e) for e in range(K + 1)]
+    dbs = [dev_batch(b) for b in bs]
+    m = sum(b.nnz for b in bs)
+    eng.reserve(n, bs[0].nnz)
+    lt = eng.locktab(m)
+    held = d.EpochBatch(torch.empty(K * n + 1, dtype=torch.int32, device=DEV),
+                        torch.empty(m, dtype=torch.int64, device=DEV), torch.empty(m, dtype=torch.uint8, device=DEV))
+    tn = tm = 0
+    for e in range(K):  # epoch e meets the commits of the epochs before it, and adds its own
+        rc = lt.lock_epoch(dbs[e], want_conflict=False)[0]
+        sel = eng.select_batch(dbs[e], rc, RC_RCOK, out=held, txn_base=tn, nnz_base=tm, want_src=False)[0]
+        tn, tm = sel.n_txn, sel.nnz
+    hk, ha = held.keys[:tm], held.acctype[:tm]
+    rows, slots, _ = lt.size()
+    cur = dbs[K]
+    rc_t = torch.empty(n, dtype=torch.uint8, device=DEV)
+    rc_h = torch.empty(n, dtype=torch.uint8, device=DEV)
+
+    def table():
+        est = lt.lock_epoch(cur, want_conflict=False, out_rc=rc_t)[2]
+        return est, lt.release(cur, rc_t, RC_RCOK)[2]  # the table is as before
+
+    def heldlist():
+        return eng.nowait_lock_epoch(cur, held=(hk, ha), want_conflict=False, out_rc=rc_h)[2]
+    for _ in range(a.warmup):
+        est, rst = table()
+        heldlist()
+        copy_ms(eng, rst["alg_bytes"])
+    same = bool(torch.equal(rc_t, rc_h))
+    te, tr, th, cp = [], [], [], []
+    for _ in range(a.steps):  # alternately: all see the same machine state
+        est, rst = table()
+        te.append(est["device_ms"])
+        tr.append(rst["device_ms"])
+        th.append(heldlist()["device_ms"])
+        cp.append(copy_ms(eng, rst["alg_bytes"]))
+    eng.set_profiling(True)
+    prof = []
+    for _ in range(5):
+        est, rst = table()
+        prof.append((lt.pass_ms(), est["phase_ms"], rst["phase_ms"], heldlist()["phase_ms"]))
+    # a rebuild: a table with room for the held rows and the epoch, its other
+    # slots taken by rows that were held once
+    rebuild = []
+    cap = max(rows + cur.nnz, tm) + 1024
+    small = eng.locktab(cap)
+    once = torch.arange(cap - rows - 512, dtype=torch.int64, device=DEV) + (1 << 40)
+    once_at = torch.zeros(once.shape[0], dtype=torch.uint8, device=DEV)
+    for _ in range(3):
+        small.clear()
+        small.acquire_rows(hk, ha)
+        small.acquire_rows(once, once_at)
+        small.release_rows(once)
+        before = small.size()
+        small.lock_epoch(cur, want_conflict=False, out_rc=rc_t)
+        if small.size()[2] > before[2]:
+            rebuild.append(small.pass_ms()["rebuild"])
+    eng.set_profiling(False)
+    small.close()
+    lt.close()
+    med = statistics.median
+    r = {"n_txn": n, "held_epochs": K, "held_requests": tm, "held_rows": rows, "slots_used": slots,
+         "rc_identical": same, "commits": est["n_commit"],
+         "table_epoch_ms": mmm(te), "heldlist_epoch_ms": mmm(th), "release_ms": mmm(tr), "copy_ms": mmm(cp),
+         "table_over_heldlist": med(te) / med(th),
+         "release_alg_bytes": rst["alg_bytes"], "release_alg_GBps": rst["alg_bytes"] / (med(tr) * 1e-3) / 1e9,
+         "release_over_copy": med(tr) / med(cp),
+         "pass_ms": {k: med(p[0][k] for p in prof) for k in ("seed", "grant")},
+         "table_phase_ms": [med(p[1][q] for p in prof) for q in range(4)],
+         "release_phase_ms": [med(p[2][q] for p in prof) for q in range(4)],
+         "heldlist_phase_ms": [med(p[3][q] for p in prof) for q in range(4)],
+         "rebuild_ms": rebuild}
+    print(f"  held {K} epoch(s): {tm} requests on {rows} rows; table epoch {fmt(r['table_epoch_ms'])}  held-list epoch "
+          f"{fmt(r['heldlist_epoch_ms'])}  table/held-list {r['table_over_heldlist']:.2f}  rc identical {same}")
+    print(f"    release {fmt(r['release_ms'])}  {r['release_alg_GBps']:.0f} GB/s  copy {fmt(r['copy_ms'])}  "
+          f"release/copy {r['release_over_copy']:.2f}  seed {r['pass_ms']['seed']:.4f}  grant "
+          f"{r['pass_ms']['grant']:.4f}  release phases {[round(x, 4) for x in r['release_phase_ms']]}  "
+          f"rebuild {[round(x, 4) for x in rebuild]}")
     return r
 
 
@@ -378,6 +478,120 @@ def closed_loop_backoff(eng, a):
     return res
 
 
+def next_epoch(eng, cur, rc, nf, out):
+    """aborted(cur) ++ the fresh txns nf, in the arrays of `out`."""
+    F = nf.n_txn
+    sel, _, sst = eng.select_batch(cur, rc, RC_ABORT, out=out, want_src=False)
+    n0, m0 = sel.n_txn, sel.nnz
+    torch.add(nf.offsets[1:], m0, out=out.offsets[n0 + 1:n0 + 1 + F])
+    out.keys[m0:m0 + nf.nnz].copy_(nf.keys)
+    out.acctype[m0:m0 + nf.nnz].copy_(nf.acctype)
+    return d.EpochBatch(out.offsets[:n0 + F + 1], out.keys[:m0 + nf.nnz], out.acctype[:m0 + nf.nnz]), sst
+
+
+def loop_hold_table(eng, fresh_dev, E, D, bufs, lt, timed):
+    """Path A: the lock table holds the commits of the last D epochs."""
+    lt.clear()
+    cur = fresh_dev[0]
+    wall, rcs, commits, stats, done = [], [], 0, [], []
+    for e in range(E):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc, _, st = lt.lock_epoch(cur, want_conflict=False)
+        commits += st["n_commit"]
+        done.append((cur, rc))
+        rst = lt.release(*done[e - D], RC_RCOK)[2] if e >= D else None
+        stats.append((st, rst))
+        if e + 1 < E:
+            cur, _ = next_epoch(eng, cur, rc, fresh_dev[e + 1], bufs[e % len(bufs)])
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        if not timed:
+            rcs.append(rc.cpu().numpy().copy())
+    return wall, rcs, commits, stats
+
+
+def loop_hold_list(eng, fresh_dev, E, D, bufs, held, timed):
+    """Path B: the held list is selected again from the last D epochs."""
+    cur = fresh_dev[0]
+    wall, rcs, commits, stats, done = [], [], 0, [], []
+    for e in range(E):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tn = tm = 0
+        for b, r in done[-D:]:
+            sel = eng.select_batch(b, r, RC_RCOK, out=held, txn_base=tn, nnz_base=tm, want_src=False)[0]
+            tn, tm = sel.n_txn, sel.nnz
+        rc, _, st = eng.nowait_lock_epoch(cur, held=(held.keys[:tm], held.acctype[:tm]) if tm else None,
+                                          want_conflict=False)
+        commits += st["n_commit"]
+        done.append((cur, rc))
+        stats.append(st)
+        if e + 1 < E:
+            cur, _ = next_epoch(eng, cur, rc, fresh_dev[e + 1], bufs[e % len(bufs)])
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        if not timed:
+            rcs.append(rc.cpu().numpy().copy())
+    return wall, rcs, commits, stats
+
+
+def closed_loop_hold(eng, a):
+    E, F, D = a.epochs, a.fresh, a.hold
+    fresh = [d.gen_ycsb(n_txn=F, zipf_theta=a.theta, seed=1000 + e) for e in range(E)]
+    fresh_dev = [dev_batch(b) for b in fresh]
+    cap_n, cap_m = E * F, sum(b.nnz for b in fresh)
+    eng.reserve(cap_n, cap_m)
+    # an epoch's arrays stay until its commits are released: D + 2 sets
+    bufs = [d.EpochBatch(torch.empty(cap_n + 1, dtype=torch.int32, device=DEV),
+                         torch.empty(cap_m, dtype=torch.int64, device=DEV),
+                         torch.empty(cap_m, dtype=torch.uint8, device=DEV)) for _ in range(D + 2)]
+    held = d.EpochBatch(torch.empty(cap_n + 1, dtype=torch.int32, device=DEV),
+                        torch.empty(cap_m, dtype=torch.int64, device=DEV),
+                        torch.empty(cap_m, dtype=torch.uint8, device=DEV))
+    lt = eng.locktab(cap_m)  # every request of the run fits: no DCC_ERANGE whatever commits
+    _, rc_a, _, _ = loop_hold_table(eng, fresh_dev, E, D, bufs, lt, timed=False)
+    _, rc_b, _, _ = loop_hold_list(eng, fresh_dev, E, D, bufs, held, timed=False)
+    same = len(rc_a) == len(rc_b) and all(np.array_equal(x, y) for x, y in zip(rc_a, rc_b))
+    for _ in range(max(a.loop_warmup - 1, 0)):
+        loop_hold_table(eng, fresh_dev, E, D, bufs, lt, timed=True)
+        loop_hold_list(eng, fresh_dev, E, D, bufs, held, timed=True)
+    wa, wb, ca, cb, sa, sb = [], [], 0, 0, [], []
+    for _ in range(a.loop_reps):  # alternately
+        w, _, c, s = loop_hold_table(eng, fresh_dev, E, D, bufs, lt, timed=True)
+        wa += w
+        ca += c
+        sa += s
+        w, _, c, s = loop_hold_list(eng, fresh_dev, E, D, bufs, held, timed=True)
+        wb += w
+        cb += c
+        sb += s
+    size = lt.size()
+    lt.close()
+    res = {"alg": "nowait", "epochs": E, "fresh": F, "theta": a.theta, "hold": D, "rc_identical": bool(same),
+           "txns_per_epoch": [int(r.size) for r in rc_a],
+           "commits_per_epoch": [int((r == RC_RCOK).sum()) for r in rc_a],
+           "table_at_end": {"rows_held": size[0], "slots_used": size[1], "rebuilds": size[2]},
+           "A_table": {"wall_ms_per_epoch": mmm(wa), "goodput_commits_per_s": ca / (sum(wa) * 1e-3),
+                       "epoch_device_ms": mmm([s[0]["device_ms"] for s in sa]),
+                       "release_device_ms": mmm([s[1]["device_ms"] for s in sa if s[1] is not None] or [0.0])},
+           "B_heldlist": {"wall_ms_per_epoch": mmm(wb), "goodput_commits_per_s": cb / (sum(wb) * 1e-3),
+                          "epoch_device_ms": mmm([s["device_ms"] for s in sb])}}
+    res["wall_B_over_A"] = res["B_heldlist"]["wall_ms_per_epoch"]["median"] / res["A_table"]["wall_ms_per_epoch"]["median"]
+    res["goodput_A_over_B"] = res["A_table"]["goodput_commits_per_s"] / res["B_heldlist"]["goodput_commits_per_s"]
+    print(f"closed loop nowait, commits held for {D} epoch(s): {E} epochs of {F} fresh txns, theta {a.theta}; txns "
+          f"per epoch {res['txns_per_epoch']}, commits {res['commits_per_epoch']}, table at the end "
+          f"{res['table_at_end']}")
+    for k in ("A_table", "B_heldlist"):
+        r = res[k]
+        print(f"  {k:10s} wall ms/epoch {fmt(r['wall_ms_per_epoch'])}  goodput {r['goodput_commits_per_s'] / 1e6:.2f} "
+              f"M commits/s  epoch device_ms {fmt(r['epoch_device_ms'])}"
+              + (f"  release device_ms {fmt(r['release_device_ms'])}" if "release_device_ms" in r else ""))
+    print(f"  wall B / A = {res['wall_B_over_A']:.2f}  goodput A / B = {res['goodput_A_over_B']:.2f}  "
+          f"rc identical {res['rc_identical']}")
+    return res
+
+
 def closed_loop(eng, a):
     E, F = a.epochs, a.fresh
     fresh = [d.gen_ycsb(n_txn=F, zipf_theta=a.theta, seed=1000 + e) for e in range(E)]
@@ -441,7 +655,11 @@ def main():
     ap.add_argument("--penalty-max", type=int, default=4)
     ap.add_argument("--queue-shapes", choices=("both", "c2", "headline", "none"), default="none")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--hold", type=int, default=0, metavar="D")
+    ap.add_argument("--table-shapes", choices=("both", "c2", "headline", "none"), default="none")
     a = ap.parse_args()
+    if a.hold and (a.alg != "nowait" or a.backoff):
+        ap.error("--hold goes with --alg nowait and without --backoff")
     assert torch.cuda.is_available(), "retry_loop needs cuda:0"
     out = {}
     with d.Engine(0) as eng:
@@ -452,9 +670,13 @@ def main():
             if a.queue_shapes in ("both", key):
                 print(f"abort queue alone, {name}:")
                 out[f"queue {name}"] = time_queue(eng, n, a)
+            if a.table_shapes in ("both", key):
+                print(f"lock table alone, {name}:")
+                out[f"table {name}"] = {f"held_{K}": time_table(eng, n, K, a) for K in (1, 4)}
     with d.Engine(0) as eng:
         if a.epochs > 0:
-            out["closed_loop"] = closed_loop_backoff(eng, a) if a.backoff else closed_loop(eng, a)
+            out["closed_loop"] = closed_loop_hold(eng, a) if a.hold else \
+                closed_loop_backoff(eng, a) if a.backoff else closed_loop(eng, a)
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
