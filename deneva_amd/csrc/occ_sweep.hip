@@ -1062,10 +1062,6 @@ __global__ __launch_bounds__(256) void k_sw_cout(SwCoutArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// k_sw_filter: list txns [pos, m) against C; survivors -> next level's list.
-// Chunks of SW_CHUNK txns are taken by ticket (so every chunk a look-back
-// waits on is held by a running workgroup); 16 waves x 64 txns per chunk.
-
 constexpr uint32_t FW = SW_CHUNK / 64;  // waves per filter workgroup
 constexpr uint32_t FK = 16;             // access rounds kept in registers (1024 accesses)
 constexpr uint32_t SW_CMP_MAXR = 4096;  // tiles of one filter workgroup

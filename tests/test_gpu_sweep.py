@@ -5,7 +5,9 @@ over the rest of the list.  The cases drive every path — level-0 access-budget
 stops, many levels and host continuations (one level per synchronisation),
 the hand-off of a low-contention list to the round solver, history-aborted
 txns inside tiles, empty and maximum-length txns, tiles with 4096 accesses —
-and the decisions must be bit-exact against the oracle's serial replay."""
+and the decisions must be bit-exact against the oracle's serial replay.
+Directed cases for single branches of the filter and the compaction are in
+test_gpu_sweep_edges.py (built by sweep_cases.py)."""
 import numpy as np
 import pytest
 
