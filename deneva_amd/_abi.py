@@ -270,6 +270,12 @@ _SIGS = [
     ("dcc_nowait_lock_epoch", C.c_int,
      [_P, C.POINTER(Batch), C.POINTER(CalvinHeld), _P, _P, C.POINTER(Stats)]),
     ("dcc_nowait_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
+    ("dcc_tso_validate_epoch", C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, C.POINTER(Stats)]),
+    ("dcc_tso_rows_set", C.c_int, [_P, _P, _P, _P, C.c_uint64]),
+    ("dcc_tso_rows_get", C.c_int, [_P, _P, _P, _P, C.c_uint64]),
+    ("dcc_tso_rows_clear", C.c_int, [_P]),
+    ("dcc_tso_rows_size", C.c_uint64, [_P]),
+    ("dcc_tso_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
     ("dcc_batch_select", C.c_int,
      [_P, C.POINTER(Batch), _P, C.c_uint8, _P, C.POINTER(SelectOut), C.POINTER(C.c_uint64),
       C.POINTER(C.c_uint64), C.POINTER(Stats)]),

@@ -474,6 +474,19 @@ struct dcc_ctx {
   int shard_groups(const uint32_t* grp, uint64_t m, uint32_t* out_dev);  // groups to batch order
   // lock tables created on this context and not yet destroyed (freed with it)
   std::vector<std::unique_ptr<dcc_locktab>> locktabs;
+  // TIMESTAMP epoch (tso.hip): the persistent row table of 32-B {key, wts, rts}
+  // slots; counters, the record of every access, txn words, the sort's
+  // ping-pong pairs, the sorted records, head slots, bounds, tile aggregates
+  // and flags, the timestamps and conflict ordinals of a host call
+  DevBuf ts_rows;
+  uint32_t ts_bits = 0;   // log2 row-table slots (0: none yet)
+  uint64_t ts_nrows = 0;  // rows in the table
+  DevBuf ts_misc, ts_arec, ts_stp, ts_k[2], ts_v[2], ts_stxn, ts_sinfo, ts_sts, ts_hslot, ts_bnd, ts_agg, ts_tdone;
+  DevBuf ts_stage, ts_conf;
+  int tso_rows_reserve(uint64_t want);
+  int tso_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
+  int tso_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* out_rc, uint32_t* out_conflict,
+                dcc_stats* st);
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes

@@ -492,6 +492,73 @@ class Engine:
                                          C.byref(st)), self._h)
         return out_rc[:n], (out_conflict[:n] if want_conflict else None), st.as_dict()
 
+    # ------------------------------------------------ TIMESTAMP (basic T/O)
+    def tso_validate_epoch(self, batch: EpochBatch, ts, want_conflict: bool = True,
+                           out_rc=None, out_conflict=None):
+        """TIMESTAMP epoch (dcc_tso_validate_epoch): returns (rc u8[n],
+        conflict u32[n] | None, stats).  ts: u64[n] timestamps, a host array
+        for a host batch, a device tensor (int64 read bit for bit) for a device
+        batch.  conflict[i] is the ordinal of the access an aborted txn aborted
+        at, ACCESS_NONE for a committed one.  The rows' wts / rts persist in the
+        context (tso_rows_*)."""
+        n = batch.n_txn
+        dev = batch.on_device
+        if ts is None:
+            ts_ptr = None
+        elif dev:
+            if not _is_device(ts):
+                raise TypeError("tso_validate_epoch: a device batch takes a device ts tensor")
+            ts_ptr = _ptr(ts) if n else _ptr(batch.offsets)
+        else:
+            ts = np.ascontiguousarray(ts, np.uint64)
+            ts_ptr = _ptr(ts) if n else _ptr(np.zeros(1, np.uint64))
+        if ts is not None and (_itemsize(ts) != 8 or ts.shape[0] < n):
+            raise ValueError("tso_validate_epoch: ts must hold n_txn 8-byte timestamps")
+        if dev:
+            import torch
+            d = batch.offsets.device
+            if out_rc is None:
+                out_rc = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
+            if want_conflict and out_conflict is None:
+                out_conflict = torch.empty(max(n, 1), dtype=torch.int32, device=d)
+        else:
+            if out_rc is None:
+                out_rc = np.empty(max(n, 1), np.uint8)
+            if want_conflict and out_conflict is None:
+                out_conflict = np.empty(max(n, 1), np.uint32)
+        if not want_conflict:
+            out_conflict = None
+        if out_rc.shape[0] < n or (out_conflict is not None and out_conflict.shape[0] < n):
+            raise ValueError("tso_validate_epoch: output buffer shorter than the epoch")
+        st = _abi.Stats()
+        b = batch.to_c()
+        _check(lib.dcc_tso_validate_epoch(self._h, C.byref(b), ts_ptr, _ptr(out_rc),
+                                          _ptr(out_conflict), C.byref(st)), self._h)
+        return out_rc[:n], (out_conflict[:n] if want_conflict else None), st.as_dict()
+
+    def tso_rows_set(self, keys, wts, rts) -> None:
+        keys = np.ascontiguousarray(keys, np.uint64)
+        w = np.ascontiguousarray(wts, np.uint64)
+        r = np.ascontiguousarray(rts, np.uint64)
+        if w.shape[0] != keys.shape[0] or r.shape[0] != keys.shape[0]:
+            raise ValueError("tso_rows_set: keys, wts and rts must have one length")
+        _check(lib.dcc_tso_rows_set(self._h, _ptr(keys), _ptr(w), _ptr(r), keys.shape[0]), self._h)
+
+    def tso_rows_get(self, keys):
+        """(wts u64[n], rts u64[n]) of the rows; (0, 0) for rows never seen."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        w = np.empty(keys.shape[0], np.uint64)
+        r = np.empty(keys.shape[0], np.uint64)
+        _check(lib.dcc_tso_rows_get(self._h, _ptr(keys), _ptr(w), _ptr(r), keys.shape[0]), self._h)
+        return w, r
+
+    def tso_rows_clear(self) -> None:
+        _check(lib.dcc_tso_rows_clear(self._h), self._h)
+
+    @property
+    def tso_rows_size(self) -> int:
+        return int(lib.dcc_tso_rows_size(self._h))
+
     # ------------------------------------------- select by decision (carry)
     def select_batch(self, batch: EpochBatch, rc, want: int = _abi.RC_ABORT, src=None, out=None,
                      txn_base: int = 0, nnz_base: int = 0, want_src: bool = True):
@@ -997,6 +1064,10 @@ def calvin_alg_bytes(n_txn: int, nnz: int, with_order: bool, with_wave: bool) ->
 
 def nowait_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
     return int(lib.dcc_nowait_alg_bytes(n_txn, nnz, int(with_conflict)))
+
+
+def tso_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
+    return int(lib.dcc_tso_alg_bytes(n_txn, nnz, int(with_conflict)))
 
 
 def select_alg_bytes(n_txn: int, n_sel: int, nnz_sel: int, n_txn_arrays: int = 0) -> int:

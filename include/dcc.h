@@ -477,6 +477,59 @@ int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const dcc_calvin
  * + 16 nnz (one lock-table slot per request) + N (RC) [+ 4N conflict]. */
 uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
 
+/* ------------------------------------------------ TIMESTAMP (basic T/O) */
+/* Epoch under CC_ALG TIMESTAMP with one txn in flight at a time: the result
+ * equals the txns of the batch running in index order, each calling get_row
+ * for its accesses in list order and then committing or aborting before the
+ * next txn starts, against Row_ts (concurrency_control/row_ts.cpp:167-266,
+ * storage/row.cpp:239-282, 371-390, system/txn.cpp:700-761).  ts[i] is the
+ * txn's timestamp (txn->get_timestamp()): any u64, in any order, ties allowed;
+ * every comparison is the reference's unsigned `<`.  Per row, wts and rts
+ * (row_ts.cpp:27-28) persist in the context across epochs; rows never seen
+ * are (0, 0).  Per access (row.cpp:252-258):
+ *   RD / SCAN  R_REQ: abort if ts < wts (row_ts.cpp:176), else
+ *              rts = max(rts, ts) (:188-189);
+ *   WR         P_REQ then R_REQ: abort if ts < rts or ts < wts (:193, :200;
+ *              TS_TWR is false, config.h:123), else rts = max(rts, ts);
+ *   XP         no request.
+ * The first aborting access ends the txn; its cleanup sends XP_REQ for the WR
+ * accesses made (txn.cpp:700-704, row.cpp:380-384), which only drops the
+ * prewrite: the rts bumps of an aborted txn stay, wts is untouched.  A txn
+ * that passes every access commits, and each of its WR accesses sends W_REQ:
+ * wts = max(wts, ts) (row_ts.cpp:237-239).  In this model no request is ever
+ * buffered or returns WAIT; Row_ts's buffered requests
+ * (concurrent txns) and TS_TWR are out of scope.
+ *   ts              [n_txn] timestamps; NULL is DCC_EINVAL
+ *   out_rc[i]       = DCC_RC_RCOK or DCC_RC_ABORT
+ *   out_conflict[i] = for an aborted txn the ordinal within the txn (0-based
+ *                     from offsets[i]) of the access that aborted it;
+ *                     DCC_ACCESS_NONE for a committed txn.  May be NULL.
+ * start_tn / finish_tn / order of the batch are ignored.  With DCC_DEVICE_PTRS
+ * the batch, ts and the outputs are device memory.  A rejected batch
+ * (malformed offsets, a txn longer than MAX_ROW_PER_TXN, the reserved key:
+ * DCC_EINVAL) leaves the row table unchanged.  One GPU: a dcc_init_multi
+ * context runs the epoch on rank 0; a communicator of more than one rank is
+ * DCC_ENOTSUP.
+ * Stats: n_commit, n_abort, nnz_w (WR accesses), n_readonly (txns with no WR
+ * access), rounds, device_ms, total_ms, alg_bytes (dcc_tso_alg_bytes); with
+ * profiling phase_ms: 0 = sort / build, 1 = round 1, 2 = rounds >= 2,
+ * 3 = final pass + table update. */
+int dcc_tso_validate_epoch(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* out_rc,
+                           uint32_t* out_conflict, dcc_stats* out_stats);
+/* Row timestamps: seed (overwrite) / read (0 for unknown rows) / forget.
+ * Host arrays of n entries.  The table holds every row that was seeded or
+ * named by an accepted batch, reached by an executed access or not (such a row
+ * is (0, 0), which reads the same as an unknown one): dcc_tso_rows_size. */
+int dcc_tso_rows_set(dcc_ctx* ctx, const uint64_t* keys, const uint64_t* wts, const uint64_t* rts,
+                     uint64_t n);
+int dcc_tso_rows_get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* wts, uint64_t* rts, uint64_t n);
+int dcc_tso_rows_clear(dcc_ctx* ctx);
+uint64_t dcc_tso_rows_size(const dcc_ctx* ctx);
+/* Algorithmic bytes of one TIMESTAMP epoch: 4(N+1) offsets + 8N timestamps
+ * + 9 nnz (key, type) + 24 nnz (one row: key, wts, rts, per access) + N (RC)
+ * [+ 4N conflict]. */
+uint64_t dcc_tso_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
+
 /* ------------------------------ NO_WAIT lock table that lives across epochs */
 /* Row_lock's NO_WAIT state where the batches live: a device-resident map
  * row -> (lock_type, owner_cnt) that epochs acquire into and finished txns
