@@ -50,6 +50,27 @@ struct DevBuf {
   void release();  // free now (a table that is dropped or replaced)
 };
 
+// A persistent row table (rowtab.h, where the methods and the kernels are):
+// 2^bits 32-byte slots {key, a, b}, linear probing with the owning engine's
+// probe policy P (dcc_device.h), at most half full.  set / get take host
+// arrays; the engines' epochs enter rows with their own kernels and add what
+// those counted to `rows`.
+struct RowTab {
+  const char* name;   // the owning engine, for messages
+  DevBuf buf, ctl;    // the slots; {error word, rows a call added}
+  uint32_t bits = 0;  // log2 slots (0: no table yet)
+  uint64_t rows = 0;  // rows in the table
+  uint32_t mask() const { return (uint32_t)((1ull << bits) - 1); }
+  uint64_t size() const { return rows; }
+  template <class P>
+  int reserve(dcc_ctx* ctx, uint64_t want);  // room for `want` rows (rehash on growth)
+  int clear(dcc_ctx* ctx);
+  template <class P>
+  int set(dcc_ctx* ctx, const uint64_t* keys, const uint64_t* a, const uint64_t* b, uint64_t n);
+  template <class P>
+  int get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* a, uint64_t* b, uint64_t n);
+};
+
 // A batch as device pointers (aliases the caller's or the ctx's staging).
 struct DevBatch {
   uint64_t n = 0, nnz = 0;
@@ -266,12 +287,9 @@ struct dcc_ctx {
   DevBuf held_keys, held_at;  // held rows of a host call (Calvin / NO_WAIT: stage_held)
   DevBuf cb_e, cb_out, cb_cnt, cb_small;           // Calvin bucket path (calvin_bucket.h)
   DevBuf snap_top, snap_aoff, snap_aidx, snap_cnt;  // captured-snapshot validation
-  DevBuf mt_rk;                                  // MaaT row table: 32-B {key, last read, last write} slots
-  uint32_t mt_bits = 0;                          // log2 row-table slots (0: none yet)
-  uint64_t mt_rows = 0;                          // rows in the table
+  RowTab mt_rows{"maat"};                        // MaaT row table: {key, last read, last write}
   uint64_t mt_new_last = 0;                      // rows the last epoch added (table sizing)
   uint64_t mt_full_redo = 0;                     // epochs run again on a bigger row table
-  uint32_t mt_rows32 = 0;                        // upload source of the row counter
   DevBuf mt_misc, mt_slot, mt_sval, mt_slot2, mt_sval2, mt_sfl, mt_stx, mt_txn, mt_agg;
   DevBuf mt_sflB, mt_stxB, mt_k1, mt_tcnt, mt_ul;
   DevBuf mt_lb;          // fused round scan: look-back status per tile (k_mt_round)
@@ -426,8 +444,7 @@ struct dcc_ctx {
   int sweep_ro(const DevBatch& d, bool big, bool scan, uint64_t nnz_w, const DevBatch* full = nullptr);
   int occ_sweep_finish(const DevBatch& d, int& next_level, bool& done, uint32_t maxlen);
   int occ_snapshot(const dcc_batch* b, const dcc_occ_snapshot* s, uint8_t* out_rc, dcc_stats* st);
-  // MaaT (maat.hip): row timestamp table + epoch workspaces
-  int maat_rows_reserve(uint64_t want);
+  // MaaT (maat.hip): epoch workspaces
   int index_reserve(uint64_t want);
   int maat_epoch(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_cts, dcc_stats* st);
   int maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_cts, dcc_stats* st, bool all_rows,
@@ -474,16 +491,13 @@ struct dcc_ctx {
   int shard_groups(const uint32_t* grp, uint64_t m, uint32_t* out_dev);  // groups to batch order
   // lock tables created on this context and not yet destroyed (freed with it)
   std::vector<std::unique_ptr<dcc_locktab>> locktabs;
-  // TIMESTAMP epoch (tso.hip): the persistent row table of 32-B {key, wts, rts}
-  // slots; counters, the record of every access, txn words, the sort's
+  // TIMESTAMP epoch (tso.hip): the persistent row table {key, wts, rts};
+  // counters, the record of every access, txn words, the sort's
   // ping-pong pairs, the sorted records, head slots, bounds, tile aggregates
   // and flags, the timestamps and conflict ordinals of a host call
-  DevBuf ts_rows;
-  uint32_t ts_bits = 0;   // log2 row-table slots (0: none yet)
-  uint64_t ts_nrows = 0;  // rows in the table
+  RowTab ts_rows{"tso"};
   DevBuf ts_misc, ts_arec, ts_stp, ts_k[2], ts_v[2], ts_stxn, ts_sinfo, ts_sts, ts_hslot, ts_bnd, ts_agg, ts_tdone;
   DevBuf ts_stage, ts_conf;
-  int tso_rows_reserve(uint64_t want);
   int tso_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
   int tso_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* out_rc, uint32_t* out_conflict,
                 dcc_stats* st);
@@ -557,4 +571,12 @@ int dcc_multi_on_rank0(dcc_ctx* ctx, bool detach, F call) {
   s->comm = cm;
   if (e != DCC_OK) ctx->last_error = s->last_error;
   return e;
+}
+// The same for any context: a one-GPU context runs the call itself, its
+// device selected.
+template <typename F>
+int dcc_on_device(dcc_ctx* ctx, bool detach, F call) {
+  if (ctx->multi) return dcc_multi_on_rank0(ctx, detach, call);
+  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
+  return call(ctx);
 }

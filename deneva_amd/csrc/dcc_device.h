@@ -1,4 +1,6 @@
-// Device-side primitives shared by the gfx950 kernels of libdcc.
+// Device-side primitives shared by the gfx950 kernels of libdcc: the per-epoch
+// hash slot, the probe loop of every open-addressing table (probe_insert /
+// probe_find with their three policies), LDS combiners, the sc1 hand-off.
 //
 // Hash-slot layout (HBM-resident open-addressing table):
 //
@@ -97,36 +99,78 @@ __device__ inline uint32_t slot_step(uint64_t key, uint32_t mask) {
   return ((uint32_t)(fmix64(key) >> 32) | 1u) & mask;
 }
 
-// Insert-or-find a write key.  Keys are never removed during an epoch, so a
-// non-empty key read by a plain (possibly L1-stale) load is exact; a stale
-// EMPTY only costs a CAS that then reports the real key.
-__device__ inline uint32_t table_insert(Slot* tab, uint32_t mask, uint64_t key) {
-  uint32_t h = slot_home(key, mask);
-  const uint32_t st = slot_step(key, mask);
-  for (uint32_t n = 0; n <= mask; n++) {
-    uint64_t cur = tab[h].key;
+// The one probe loop of every open-addressing table here (this header's Slot,
+// locktab.hip's LtSlot, rowtab.h's RowSlot: anything whose first member is a
+// u64 key, KEY_EMPTY when free).  A probe policy P supplies
+//   home(key, mask), step(key, mask)   the walk h, h + step, ... (mod mask + 1)
+//   walk_last                          the walk gives up after walk_last + 1 slots
+//                                      (and after mask + 1: the whole table)
+//   none                               what a walk that ran out returns; the
+//                                      caller decides what that means
+// Keys are never removed in place, so a non-empty key read by a plain
+// (possibly L1-stale) load is exact; a stale EMPTY only costs a CAS that then
+// reports the real key.
+struct ProbeDouble {  // double hashing (above), the whole table
+  static constexpr uint32_t walk_last = ~0u, none = SID_NONE;
+  __device__ static uint32_t home(uint64_t key, uint32_t mask) { return slot_home(key, mask); }
+  __device__ static uint32_t step(uint64_t key, uint32_t mask) { return slot_step(key, mask); }
+};
+constexpr uint32_t ROW_NONE = 0xFFFFFFFFu;  // a row table has up to 2^31 slots
+constexpr uint32_t MT_WALK = 256;  // MaaT's walk bound: past it the epoch runs again on a bigger table
+struct ProbeFib {  // unit step from the Fibonacci home (the top bits of the product), MT_WALK slots
+  static constexpr uint32_t walk_last = MT_WALK - 1, none = ROW_NONE;
+  __device__ static uint32_t home(uint64_t key, uint32_t mask) {
+    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) >> __builtin_clz(mask);
+  }
+  __device__ static uint32_t step(uint64_t, uint32_t) { return 1u; }
+};
+struct ProbeMix {  // unit step from the fmix64 home, the whole table
+  static constexpr uint32_t walk_last = ~0u, none = ROW_NONE;
+  __device__ static uint32_t home(uint64_t key, uint32_t mask) { return (uint32_t)fmix64(key) & mask; }
+  __device__ static uint32_t step(uint64_t, uint32_t) { return 1u; }
+};
+
+// Insert-or-find `key`; claimed: this call took an empty slot.
+template <class P, class S>
+__device__ inline uint32_t probe_insert(S* tab, uint32_t mask, uint64_t key, bool& claimed) {
+  uint32_t h = P::home(key, mask);
+  const uint32_t st = P::step(key, mask), last = P::walk_last < mask ? P::walk_last : mask;
+  claimed = false;
+  for (uint32_t n = 0; n <= last; n++) {
+    const uint64_t cur = tab[h].key;
     if (cur == key) return h;
     if (cur == KEY_EMPTY) {
-      uint64_t prev = atomicCAS((unsigned long long*)&tab[h].key, (unsigned long long)KEY_EMPTY,
-                                (unsigned long long)key);
+      const uint64_t prev = atomicCAS((unsigned long long*)&tab[h].key, (unsigned long long)KEY_EMPTY,
+                                      (unsigned long long)key);
+      if (prev == KEY_EMPTY) claimed = true;
       if (prev == KEY_EMPTY || prev == key) return h;
     }
     h = (h + st) & mask;
   }
-  return SID_NONE;  // table full: host sizing guarantees this never happens
+  return P::none;
 }
-
 // Find a key inserted by an earlier kernel (read-only probe).
-__device__ inline uint32_t table_find(const Slot* tab, uint32_t mask, uint64_t key) {
-  uint32_t h = slot_home(key, mask);
-  const uint32_t st = slot_step(key, mask);
-  for (uint32_t n = 0; n <= mask; n++) {
+template <class P, class S>
+__device__ inline uint32_t probe_find(const S* tab, uint32_t mask, uint64_t key) {
+  uint32_t h = P::home(key, mask);
+  const uint32_t st = P::step(key, mask), last = P::walk_last < mask ? P::walk_last : mask;
+  for (uint32_t n = 0; n <= last; n++) {
     const uint64_t cur = tab[h].key;
     if (cur == key) return h;
-    if (cur == KEY_EMPTY) return SID_NONE;
+    if (cur == KEY_EMPTY) return P::none;
     h = (h + st) & mask;
   }
-  return SID_NONE;
+  return P::none;
+}
+
+// The per-epoch table's write keys (SID_NONE, table full: host sizing
+// guarantees this never happens).
+__device__ inline uint32_t table_insert(Slot* tab, uint32_t mask, uint64_t key) {
+  bool claimed;
+  return probe_insert<ProbeDouble>(tab, mask, key, claimed);
+}
+__device__ inline uint32_t table_find(const Slot* tab, uint32_t mask, uint64_t key) {
+  return probe_find<ProbeDouble>(tab, mask, key);
 }
 
 // atomicMin with a read filter: hot keys see one real atomic per round instead

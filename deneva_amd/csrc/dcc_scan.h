@@ -16,7 +16,7 @@
 // one u64, low and high word: one loop, both shuffles of a step back to back.
 //
 // Barrier contract of block_excl / block_reduce (s_w: one LDS element per
-// wave, the caller's, so no kernel's LDS size depends on this header):
+// wave, the caller's, so no kernel's LDS size depends on them):
 //   on entry   no wave still reads s_w from an earlier use.  True for the
 //              first use in a kernel; a caller that reuses s_w (a loop, two
 //              scans in a row) puts a barrier before the call;
@@ -170,6 +170,16 @@ __device__ inline typename Op::T block_reduce_reuse(typename Op::T v, typename O
                                                     uint32_t nw) {
   Sync::sync();
   return block_reduce<Op, Sync>(v, s_w, nw);
+}
+
+// One atomic per workgroup (NW waves) for a per-thread count.  The one
+// template here with LDS words of its own (NW, per kernel that calls it): a
+// second call in a kernel comes behind a barrier.
+template <uint32_t NW>
+__device__ inline void block_add(uint32_t c, uint32_t* ctr) {
+  __shared__ uint32_t s_c[NW];
+  const uint32_t v = block_reduce<NW, AddOp<uint32_t>>(c, s_c);
+  if (threadIdx.x == 0 && v) atomicAdd(ctr, v);
 }
 
 }  // namespace dcc

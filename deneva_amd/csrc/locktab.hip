@@ -4,8 +4,8 @@
 // is the grant pass of an epoch, lock_release (:240-256: owner_cnt--, LOCK_NONE
 // at zero) is dcc_locktab_release.
 //
-// The table is open addressing over 2^k 16-byte slots with the hashing of
-// dcc_device.h:
+// The table is open addressing over 2^k 16-byte slots with the probe loop
+// and the double hashing (ProbeDouble) of dcc_device.h:
 //
 //   struct LtSlot { u64 key; u32 word; u32 rel; }
 //     word  EX:1 | owner_cnt:31     0: LOCK_NONE
@@ -73,35 +73,13 @@ constexpr uint32_t LT_C_ERR = 0, LT_C_NEW = 1, LT_C_ROWS = 2, LT_C_HOLDS = 3, LT
                    LT_C_SELM = 6, LT_C_OUT = 7, LT_C_WORDS = 8;
 constexpr uint32_t LT_ERR_OFF = 1, LT_ERR_KEY = 2, LT_ERR_MISS = 4, LT_ERR_OVER = 8, LT_ERR_FULL = 16;
 
-// table_insert of dcc_device.h; claimed: this call took an empty slot
+// the probes of dcc_device.h; SID_NONE from the insert: full, which the
+// host's room check (at most half full) keeps from happening
 __device__ inline uint32_t lt_insert(LtSlot* tab, uint32_t mask, uint64_t key, bool& claimed) {
-  uint32_t h = slot_home(key, mask);
-  const uint32_t st = slot_step(key, mask);
-  claimed = false;
-  for (uint32_t n = 0; n <= mask; n++) {
-    const uint64_t cur = tab[h].key;
-    if (cur == key) return h;
-    if (cur == KEY_EMPTY) {
-      const uint64_t prev = atomicCAS((unsigned long long*)&tab[h].key, (unsigned long long)KEY_EMPTY,
-                                      (unsigned long long)key);
-      if (prev == KEY_EMPTY) claimed = true;
-      if (prev == KEY_EMPTY || prev == key) return h;
-    }
-    h = (h + st) & mask;
-  }
-  return SID_NONE;  // full: the host's room check keeps the table at most half full
+  return probe_insert<ProbeDouble>(tab, mask, key, claimed);
 }
-
 __device__ inline uint32_t lt_find(const LtSlot* tab, uint32_t mask, uint64_t key) {
-  uint32_t h = slot_home(key, mask);
-  const uint32_t st = slot_step(key, mask);
-  for (uint32_t n = 0; n <= mask; n++) {
-    const uint64_t cur = tab[h].key;
-    if (cur == key) return h;
-    if (cur == KEY_EMPTY) return SID_NONE;
-    h = (h + st) & mask;
-  }
-  return SID_NONE;
+  return probe_find<ProbeDouble>(tab, mask, key);
 }
 
 // Per-workgroup combiner of the adds to table words: the adds of one slot are
@@ -728,9 +706,7 @@ template <typename F>
 static int lt_run(dcc_locktab* lt, bool detach, F call) {
   dcc_ctx* ctx = lt->owner;
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
-  if (ctx->multi) return dcc_multi_on_rank0(ctx, detach, call);
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  return call(ctx);
+  return dcc_on_device(ctx, detach, call);
 }
 
 extern "C" int dcc_locktab_create(dcc_ctx* ctx, const dcc_locktab_params* params, dcc_locktab** out) {

@@ -24,8 +24,9 @@
 // undecided txn always decides, so the rounds terminate.
 //
 // Row timestamps (timestamp_last_read / _write, row_maat.h:38-39) persist
-// in an HBM open-addressing table across epochs; committed txns raise them
-// with atomicMax at the end of the epoch (row_maat.cpp:249-251, 276-278).
+// across epochs in the context's row table (rowtab.h, probe policy ProbeFib);
+// committed txns raise them with atomicMax at the end of the epoch
+// (row_maat.cpp:249-251, 276-278).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +41,7 @@
 #include "dcc_env.h"
 #include "occ_kernels.h"
 #include "radix_sort.h"
+#include "rowtab.h"
 
 using namespace dcc;
 
@@ -57,113 +59,13 @@ constexpr uint8_t ST_UND = 0, ST_COM = 1, ST_ABO = 2;
 constexpr uint8_t F_R = 1, F_W = 2, F_LAST = 4, F_START = 8;
 constexpr uint32_t MT_ERR_OFF = 1, MT_ERR_KEY = 2, MT_ERR_FULL = 4;
 
-__device__ inline uint64_t mt_hash(uint64_t key, uint32_t bits) {
-  return (key * 0x9E3779B97F4A7C15ull) >> (64 - bits);
-}
-
 // ---------------------------------------------------------------- row table
-// One 32-B slot per row: the key and its two timestamps side by side, so the
-// access that finds a row has its timestamps in the same 64-B line (three
-// separate arrays cost three random HBM lines per access).
-struct __attribute__((aligned(32))) MtSlot {
-  uint64_t key, lr, lw, pad;
-};
-static_assert(sizeof(MtSlot) == 32, "row slot");
-// insert-or-find the row of `key` (ins: this call created it); its lr / lw
-// stay 0 until an epoch commits
-// (a walk past MT_WALK slots reports MT_ERR_FULL: the host grows the table
-// and runs the epoch again)
-constexpr uint64_t MT_WALK = 256;
-__device__ inline uint32_t mt_row(MtSlot* rt, uint32_t bits, uint64_t key, bool& ins,
-                                  uint32_t* err) {
-  const uint64_t mask = (1ull << bits) - 1;
-  uint64_t s = mt_hash(key, bits);
-  ins = false;
-  for (uint64_t q = 0; q <= mask && q < MT_WALK; q++) {
-    const uint64_t v = rt[s].key;
-    if (v == key) return (uint32_t)s;
-    if (v == DCC_KEY_RESERVED) {
-      const unsigned long long prev = atomicCAS((unsigned long long*)&rt[s].key,
-                                                (unsigned long long)DCC_KEY_RESERVED,
-                                                (unsigned long long)key);
-      if (prev == DCC_KEY_RESERVED) {
-        ins = true;
-        return (uint32_t)s;
-      }
-      if (prev == key) return (uint32_t)s;
-    }
-    s = (s + 1) & mask;
-  }
-  atomicOr(err, MT_ERR_FULL);
-  return 0;
-}
-
-// one atomic per workgroup for a per-thread count (256 threads)
-__device__ inline void block_add(uint32_t c, uint32_t* ctr) {
-  __shared__ uint32_t s_c[4];
-  const uint32_t v = block_reduce<4, AddOp<uint32_t>>(c, s_c);
-  if (threadIdx.x == 0 && v) atomicAdd(ctr, v);
-}
-
-// rehash: every row of the old table into the new one (values carried)
-__global__ __launch_bounds__(256) void k_mt_rehash(const MtSlot* ot, uint64_t ocap, MtSlot* nt,
-                                                   uint32_t nbits, uint32_t* nrows, uint32_t* err) {
-  uint32_t c = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < ocap; i += (uint64_t)gridDim.x * 256) {
-    const MtSlot o = ot[i];
-    if (o.key == DCC_KEY_RESERVED) continue;
-    bool ins;
-    const uint32_t s = mt_row(nt, nbits, o.key, ins, err);
-    c += ins;
-    nt[s].lr = o.lr;
-    nt[s].lw = o.lw;
-  }
-  block_add(c, nrows);
-}
-// an empty table: every key KEY_RESERVED, timestamps 0
-__global__ __launch_bounds__(256) void k_mt_clear(MtSlot* rt, uint64_t cap) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256)
-    rt[i] = MtSlot{DCC_KEY_RESERVED, 0, 0, 0};
-}
-
-// host-seeded rows (dcc_maat_rows_set): insert and overwrite the timestamps
-__global__ __launch_bounds__(256) void k_mt_seed(const uint64_t* keys, const uint64_t* lr,
-                                                 const uint64_t* lw, uint64_t n, MtSlot* rt,
-                                                 uint32_t bits, uint32_t* nrows, uint32_t* err) {
-  uint32_t c = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-    if (keys[i] == DCC_KEY_RESERVED) {
-      atomicOr(err, MT_ERR_KEY);
-      continue;
-    }
-    bool ins;
-    const uint32_t s = mt_row(rt, bits, keys[i], ins, err);
-    c += ins;
-    rt[s].lr = lr[i];
-    rt[s].lw = lw[i];
-  }
-  block_add(c, nrows);
-}
-__global__ __launch_bounds__(256) void k_mt_get(const uint64_t* keys, uint64_t n, const MtSlot* rt,
-                                                uint32_t bits, uint64_t* lr, uint64_t* lw) {
-  const uint64_t mask = (1ull << bits) - 1;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-    const uint64_t key = keys[i];
-    uint64_t s = mt_hash(key, bits), a = 0, b = 0;
-    for (uint64_t q = 0; q <= mask; q++) {
-      const uint64_t v = rt[s].key;
-      if (v == key) {
-        a = rt[s].lr;
-        b = rt[s].lw;
-        break;
-      }
-      if (v == DCC_KEY_RESERVED) break;
-      s = (s + 1) & mask;
-    }
-    lr[i] = a;
-    lw[i] = b;
-  }
-}
+// rowtab.h's slot {key, a, b}: a row's timestamp_last_read / _write, 0 until
+// an epoch commits (rt[s].*LR).  A walk past MT_WALK slots finds no row
+// (ROW_NONE): the access reports MT_ERR_FULL, the host grows the table and
+// runs the epoch again.
+using MtProbe = ProbeFib;
+constexpr auto LR = &RowSlot::a, LW = &RowSlot::b;
 
 // ---------------------------------------------------------------- check
 // The batch's validity before the persistent row table changes: offsets
@@ -202,8 +104,8 @@ struct BaseArgs {
   const uint8_t* at;
   uint32_t rw_all;
   const uint64_t* keys;
-  MtSlot* rt;
-  uint32_t bits;
+  RowSlot* rt;
+  uint32_t mask;
   uint32_t* slot;   // [nnz] row slot per access
   uint32_t* slot2;  // [nnz] the same (the sort's first key buffer)
   uint32_t* nrows;
@@ -260,15 +162,17 @@ __global__ __launch_bounds__(256) void k_mt_base(BaseArgs a) {
       sl[u] = 0;
       if (x0 + 64 * u + lane < a1 && key[u] != DCC_KEY_RESERVED) {  // the check rejected reserved keys
         bool ins;
-        sl[u] = mt_row(a.rt, a.bits, key[u], ins, a.err);
+        const uint32_t s = probe_insert<MtProbe>(a.rt, a.mask, key[u], ins);
+        if (s == ROW_NONE) atomicOr(a.err, MT_ERR_FULL);  // slot 0 is read below; the finish writes nothing
+        else sl[u] = s;
         nins += ins;
       }
     }
     uint64_t lw[4], lr[4];
 #pragma unroll
     for (uint32_t u = 0; u < 4; u++) {
-      lw[u] = a.rt[sl[u]].lw;
-      lr[u] = a.rt[sl[u]].lr;
+      lw[u] = a.rt[sl[u]].*LW;
+      lr[u] = a.rt[sl[u]].*LR;
     }
 #pragma unroll
     for (uint32_t u = 0; u < 4; u++) {
@@ -718,7 +622,7 @@ struct FinArgs {
   const uint8_t* state;
   const uint64_t* cts;
   const uint32_t* slot;
-  MtSlot* rt;
+  RowSlot* rt;
   uint8_t* rc;
   uint64_t* cts_out;
   uint32_t* cnt;  // [0] commits, [1] undecided, [2] write accesses
@@ -744,8 +648,8 @@ __global__ __launch_bounds__(256) void k_mt_finish(FinArgs a) {
       nw += ty == DCC_WR;
       if (!ok || !keep) continue;
       const uint32_t sl = a.slot[x];
-      if (a.rw_all || ty == DCC_RD) atomicMax((unsigned long long*)&a.rt[sl].lr, c);
-      if (a.rw_all || ty == DCC_WR) atomicMax((unsigned long long*)&a.rt[sl].lw, c);
+      if (a.rw_all || ty == DCC_RD) atomicMax((unsigned long long*)&(a.rt[sl].*LR), c);
+      if (a.rw_all || ty == DCC_WR) atomicMax((unsigned long long*)&(a.rt[sl].*LW), c);
     }
   }
   com = wave_reduce<AddOp<uint32_t>>(com);
@@ -1006,36 +910,6 @@ __global__ __launch_bounds__(256) void k_mt_gscatter(const uint32_t* off, uint64
 }
 
 // ---------------------------------------------------------------- host
-// Row table capacity for `want` rows at <= 50 % load (rehash on growth).
-int dcc_ctx::maat_rows_reserve(uint64_t want) {
-  dcc_ctx* ctx = this;
-  uint32_t* cnt = (uint32_t*)mt_misc.p;  // [0] rows, [1] errors
-  if (mt_bits && (2 * want) <= (1ull << mt_bits)) return DCC_OK;
-  uint32_t bits = std::max<uint32_t>(mt_bits, 12);
-  while ((1ull << bits) < 2 * want) bits++;
-  if (bits > 31) return fail(DCC_ERANGE, "maat: row table exceeds 2^31 slots");
-  const uint64_t cap = 1ull << bits;
-  DevBuf nt;
-  CR(nt.ensure(this, cap * sizeof(MtSlot), "maat row table"));
-  k_mt_clear<<<g1(cap, 16384), 256, 0, stream>>>((MtSlot*)nt.p, cap);
-  CK(hipMemsetAsync(cnt, 0, 8, stream));
-  if (mt_bits) {
-    const uint64_t ocap = 1ull << mt_bits;
-    k_mt_rehash<<<g1(ocap), 256, 0, stream>>>((const MtSlot*)mt_rk.p, ocap, (MtSlot*)nt.p, bits, cnt,
-                                              cnt + 1);
-  }
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(hmisc, cnt + 1, 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  mt_rk = std::move(nt);
-  mt_bits = bits;
-  if (*(const uint32_t*)hmisc & MT_ERR_FULL) {  // a rehash walk ran past MT_WALK: bigger still
-    CK(hipMemsetAsync(cnt + 1, 0, 4, stream));
-    return maat_rows_reserve(2 * want);
-  }
-  return DCC_OK;
-}
-
 // The row table is sized for the rows the epoch is expected to add (the last
 // epoch's count with a quarter of headroom, a quarter of the accesses the
 // first time) instead of one row per access: at the headline 3.3 M distinct
@@ -1069,17 +943,13 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
   CR(stage_batch(b, d));
   const uint64_t n = d.n, m = d.nnz;
   CR(mt_misc.ensure(this, 64 + MT_RING * 4, "maat counters"));
-  uint32_t* cnt = (uint32_t*)mt_misc.p;  // [0] rows, [1] err, [2..4] finish counts, ring at 8
+  uint32_t* cnt = (uint32_t*)mt_misc.p;  // [0] rows added, [1] err, [2..4] finish counts, ring at 8
   uint32_t* ring = cnt + 8;
-  // the row counter survives between epochs in mt_rows (host copy)
   {
     const uint64_t est = mt_new_last ? mt_new_last + mt_new_last / 4 + 4096 : m / 4 + 4096;
-    CR(maat_rows_reserve(mt_rows + (all_rows ? m : std::min<uint64_t>(m, est))));
+    CR(mt_rows.reserve<MtProbe>(this, mt_rows.rows + (all_rows ? m : std::min<uint64_t>(m, est))));
   }
-  const uint64_t rows_before = mt_rows;
-  mt_rows32 = (uint32_t)mt_rows;
-  CK(hipMemcpyAsync(cnt, &mt_rows32, 4, hipMemcpyHostToDevice, stream));
-  CK(hipMemsetAsync(cnt + 1, 0, 4 * 7 + MT_RING * 4, stream));
+  CK(hipMemsetAsync(cnt, 0, 4 * 8 + MT_RING * 4, stream));
   const uint64_t mm = std::max<uint64_t>(m, 1);
   CR(mt_slot.ensure(this, mm * 4, "maat slots"));
   CR(mt_sval.ensure(this, mm * 4, "maat sort values"));
@@ -1137,7 +1007,7 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
   CK(hipEventRecord(ev0, stream));
   // the check passed: the offsets cover every access once, so the base pass
   // writes every slot and sort value (no clears)
-  BaseArgs ba{n,     m,     d.off, d.acctype, rw_all, d.keys, (MtSlot*)mt_rk.p, mt_bits,
+  BaseArgs ba{n,     m,     d.off, d.acctype, rw_all, d.keys, (RowSlot*)mt_rows.buf.p, mt_rows.mask(),
               (uint32_t*)mt_slot.p, (uint32_t*)mt_slot2.p, cnt, (uint32_t*)mt_sval.p,
               base,  state, lacc,  uacc,      pend,   cnt + 1};
   k_mt_base<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(ba);  // a wave per 64 txns
@@ -1151,7 +1021,7 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
   auto sort_groups = [&](uint64_t mm) {
     uint32_t* kk[2] = {(uint32_t*)mt_slot2.p, (uint32_t*)mt_k1.p};
     uint32_t* vb[2] = {(uint32_t*)mt_sval.p, (uint32_t*)mt_sval2.p};
-    const int cur = mm ? radix_sort_u32(kk, vb, mm, mt_bits, (uint32_t*)cv_scratch.p, stream) : 0;
+    const int cur = mm ? radix_sort_u32(kk, vb, mm, mt_rows.bits, (uint32_t*)cv_scratch.p, stream) : 0;
     ssb[0] = kk[cur];
     ssb[1] = kk[cur ^ 1];
     if (mm) k_mt_groups<<<g1(mm), 256, 0, stream>>>(ssb[0], vb[cur], mm, sflb[0], stxb[0]);
@@ -1337,7 +1207,7 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
     CR(solve(m, nullptr, nullptr, n, 0));
   }
   FinArgs fa{n, m, d.off, d.acctype, rw_all, state, cts, (const uint32_t*)mt_slot.p,
-             (MtSlot*)mt_rk.p, rc_dev, cts_dev, cnt + 2, cnt + 1};
+             (RowSlot*)mt_rows.buf.p, rc_dev, cts_dev, cnt + 2, cnt + 1};
   k_mt_finish<<<g1(n, 2048), 256, 0, stream>>>(fa);
   CK(hipGetLastError());
   CK(hipEventRecord(ev1, stream));
@@ -1348,7 +1218,7 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
   CK(hipMemcpyAsync(hmisc, cnt, 32, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
-  mt_rows = hc[0];  // rows inserted this epoch stay in the table whatever follows
+  mt_rows.rows += hc[0];  // rows inserted this epoch stay in the table whatever follows
   if (hc[1] & MT_ERR_OFF) return fail(DCC_EINVAL, "batch: malformed offsets");
   if (hc[1] & MT_ERR_KEY) return fail(DCC_EINVAL, "batch: key equal to DCC_KEY_RESERVED");
   if (hc[1] & MT_ERR_FULL) {
@@ -1357,7 +1227,7 @@ int dcc_ctx::maat_epoch_try(const dcc_batch* b, uint8_t* out_rc, uint64_t* out_c
   }
   if (hc[1] & MT_ERR_SPIN) return fail(DCC_EIO, "maat: round scan look-back timed out");
   if (hc[3]) return fail(DCC_EIO, "maat: %u undecided transactions", hc[3]);
-  mt_new_last = mt_rows - rows_before;
+  mt_new_last = hc[0];
   S.rounds = rounds;
   S.n_commit = hc[2];
   S.n_abort = n - hc[2];
@@ -1377,87 +1247,31 @@ extern "C" uint64_t dcc_maat_alg_bytes(uint64_t n_txn, uint64_t nnz) {
 extern "C" int dcc_maat_validate_epoch(dcc_ctx* ctx, const dcc_batch* batch, uint8_t* out_rc,
                                        uint64_t* out_commit_ts, dcc_stats* out_stats) {
   if (!ctx) return DCC_EINVAL;
-  if (ctx->multi)  // the whole epoch on rank 0 (dcc_multi.cpp): no collective
-    return dcc_multi_on_rank0(ctx, true, [&](dcc_ctx* s) {
-      return s->maat_epoch(batch, out_rc, out_commit_ts, out_stats);
-    });
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  return ctx->maat_epoch(batch, out_rc, out_commit_ts, out_stats);
+  // a multi-GPU context: the whole epoch on rank 0 (dcc_multi.cpp), no collective
+  return dcc_on_device(ctx, true,
+                       [&](dcc_ctx* s) { return s->maat_epoch(batch, out_rc, out_commit_ts, out_stats); });
 }
 
 extern "C" int dcc_maat_rows_clear(dcc_ctx* ctx) {
   if (!ctx) return DCC_EINVAL;
-  if (ctx->multi) return dcc_multi_on_rank0(ctx, false, dcc_maat_rows_clear);
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  if (ctx->mt_bits) {
-    const uint64_t cap = 1ull << ctx->mt_bits;
-    k_mt_clear<<<g1(cap, 16384), 256, 0, ctx->stream>>>((MtSlot*)ctx->mt_rk.p, cap);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-      return ctx->hip_fail(hipGetLastError(), "maat rows clear");
-  }
-  ctx->mt_rows = 0;
-  return DCC_OK;
+  return dcc_on_device(ctx, false, [](dcc_ctx* s) { return s->mt_rows.clear(s); });
 }
 
 extern "C" int dcc_maat_rows_set(dcc_ctx* ctx, const uint64_t* keys, const uint64_t* last_read,
                                  const uint64_t* last_write, uint64_t n) {
   if (!ctx || (n && (!keys || !last_read || !last_write))) return DCC_EINVAL;
-  if (ctx->multi)
-    return dcc_multi_on_rank0(ctx, false,
-                              [&](dcc_ctx* s) { return dcc_maat_rows_set(s, keys, last_read, last_write, n); });
-  if (n == 0) return DCC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  CR(ctx->mt_misc.ensure(ctx, 64 + MT_RING * 4, "maat counters"));
-  CR(ctx->maat_rows_reserve(ctx->mt_rows + n));
-  DevBuf tmp;
-  CR(tmp.ensure(ctx, n * 24, "maat seed"));
-  uint64_t* t = (uint64_t*)tmp.p;
-  uint32_t* cnt = (uint32_t*)ctx->mt_misc.p;
-  ctx->mt_rows32 = (uint32_t)ctx->mt_rows;
-  CK(hipMemcpyAsync(cnt, &ctx->mt_rows32, 4, hipMemcpyHostToDevice, ctx->stream));
-  CK(hipMemsetAsync(cnt + 1, 0, 4, ctx->stream));
-  CK(hipMemcpyAsync(t, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  CK(hipMemcpyAsync(t + n, last_read, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  CK(hipMemcpyAsync(t + 2 * n, last_write, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  k_mt_seed<<<g1(n), 256, 0, ctx->stream>>>(t, t + n, t + 2 * n, n, (MtSlot*)ctx->mt_rk.p,
-                                            ctx->mt_bits, cnt, cnt + 1);
-  CK(hipGetLastError());
-  uint32_t hc[2];
-  CK(hipMemcpyAsync(hc, cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-  CK(hipStreamSynchronize(ctx->stream));
-  if (hc[1] & MT_ERR_KEY) return ctx->fail(DCC_EINVAL, "maat rows: key equal to DCC_KEY_RESERVED");
-  if (hc[1] & MT_ERR_FULL) return ctx->fail(DCC_EIO, "maat: row table full");
-  ctx->mt_rows = hc[0];
-  return DCC_OK;
+  return dcc_on_device(ctx, false,
+                       [&](dcc_ctx* s) { return s->mt_rows.set<MtProbe>(s, keys, last_read, last_write, n); });
 }
 
 extern "C" int dcc_maat_rows_get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* last_read,
                                  uint64_t* last_write, uint64_t n) {
   if (!ctx || (n && (!keys || !last_read || !last_write))) return DCC_EINVAL;
-  if (ctx->multi)
-    return dcc_multi_on_rank0(ctx, false,
-                              [&](dcc_ctx* s) { return dcc_maat_rows_get(s, keys, last_read, last_write, n); });
-  if (n == 0) return DCC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  if (!ctx->mt_bits) {
-    memset(last_read, 0, n * 8);
-    memset(last_write, 0, n * 8);
-    return DCC_OK;
-  }
-  DevBuf tmp;
-  CR(tmp.ensure(ctx, n * 24, "maat get"));
-  uint64_t* t = (uint64_t*)tmp.p;
-  CK(hipMemcpyAsync(t, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  k_mt_get<<<g1(n), 256, 0, ctx->stream>>>(t, n, (const MtSlot*)ctx->mt_rk.p, ctx->mt_bits,
-                                           t + n, t + 2 * n);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(last_read, t + n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  CK(hipMemcpyAsync(last_write, t + 2 * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  CK(hipStreamSynchronize(ctx->stream));
-  return DCC_OK;
+  return dcc_on_device(ctx, false,
+                       [&](dcc_ctx* s) { return s->mt_rows.get<MtProbe>(s, keys, last_read, last_write, n); });
 }
 
 extern "C" uint64_t dcc_maat_rows_size(const dcc_ctx* ctx) {
-  if (ctx && ctx->multi) return dcc_multi_sub((dcc_ctx*)ctx, 0)->mt_rows;
-  return ctx ? ctx->mt_rows : 0;
+  if (ctx && ctx->multi) ctx = dcc_multi_sub((dcc_ctx*)ctx, 0);
+  return ctx ? ctx->mt_rows.size() : 0;
 }

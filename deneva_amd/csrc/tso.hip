@@ -1,5 +1,6 @@
 // Basic timestamp ordering (CC_ALG TIMESTAMP) for a whole epoch
-// (dcc_tso_validate_epoch), with the rows' wts / rts persistent in the context.
+// (dcc_tso_validate_epoch), with the rows' wts / rts persistent in the
+// context's row table (rowtab.h, probe policy ProbeMix).
 //
 // Reference: the txns of the batch run in index order, each one atomically:
 // get_row for its accesses in list order (storage/row.cpp:239-282: WR sends
@@ -59,6 +60,7 @@
 #include "nowait_lanes.h"
 #include "occ_kernels.h"
 #include "radix_sort.h"
+#include "rowtab.h"
 
 using namespace dcc;
 
@@ -74,101 +76,17 @@ constexpr uint32_t TS_ERR_OFF = 1, TS_ERR_KEY = 2, TS_ERR_FULL = 4, TS_ERR_STATE
 constexpr uint32_t TS_C_ERR = 0, TS_C_MAXLEN = 1, TS_C_NWR = 2, TS_C_RO = 3, TS_C_COMMIT = 4,
                    TS_C_HEADS = 5, TS_C_ROWS = 6, TS_C_KOR = 8, TS_C_KNOR = 10, TS_C_RING = 16,
                    TS_C_WORDS = TS_C_RING + TS_RING;
-constexpr uint32_t TS_NONE = 0xFFFFFFFFu;
+constexpr uint32_t TS_NONE = ROW_NONE;
 // sorted record word: position | type << 8 | head << 16 | last << 17
 constexpr uint32_t TS_I_HEAD = 1u << 16, TS_I_LAST = 1u << 17;
 // txn word: state << 8 | progress
 __device__ inline uint32_t st_state(uint32_t w) { return w >> 8; }
 __device__ inline uint32_t st_prog(uint32_t w) { return w & 0xFFu; }
 
-// One row of the persistent table: open addressing, linear probing, <= 50 % full.
-struct __attribute__((aligned(32))) TsRow {
-  uint64_t key, wts, rts, pad;
-};
-__device__ inline uint32_t ts_home(uint64_t key, uint32_t mask) { return (uint32_t)fmix64(key) & mask; }
-__device__ inline uint32_t ts_row_insert(TsRow* tab, uint32_t mask, uint64_t key, bool& ins) {
-  uint32_t h = ts_home(key, mask);
-  ins = false;
-  for (uint32_t q = 0; q <= mask; q++) {
-    const uint64_t cur = tab[h].key;
-    if (cur == key) return h;
-    if (cur == KEY_EMPTY) {
-      const uint64_t prev = atomicCAS((unsigned long long*)&tab[h].key, (unsigned long long)KEY_EMPTY,
-                                      (unsigned long long)key);
-      if (prev == KEY_EMPTY) {
-        ins = true;
-        return h;
-      }
-      if (prev == key) return h;
-    }
-    h = (h + 1) & mask;
-  }
-  return TS_NONE;
-}
-__device__ inline uint32_t ts_row_find(const TsRow* tab, uint32_t mask, uint64_t key) {
-  uint32_t h = ts_home(key, mask);
-  for (uint32_t q = 0; q <= mask; q++) {
-    const uint64_t cur = tab[h].key;
-    if (cur == key) return h;
-    if (cur == KEY_EMPTY) return TS_NONE;
-    h = (h + 1) & mask;
-  }
-  return TS_NONE;
-}
-
-// one atomic per workgroup for a per-thread count (TS_T threads)
-__device__ inline void ts_block_add(uint32_t c, uint32_t* ctr) {
-  __shared__ uint32_t s_c[TS_T / 64];
-  const uint32_t v = block_reduce<TS_T / 64, AddOp<uint32_t>>(c, s_c);
-  if (threadIdx.x == 0 && v) atomicAdd(ctr, v);
-}
-
-// ------------------------------------------------------------ row table
-__global__ __launch_bounds__(TS_T) void k_ts_clear(TsRow* rt, uint64_t cap) {
-  for (uint64_t i = (uint64_t)blockIdx.x * TS_T + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * TS_T)
-    rt[i] = TsRow{KEY_EMPTY, 0, 0, 0};
-}
-__global__ __launch_bounds__(TS_T) void k_ts_rehash(const TsRow* ot, uint64_t ocap, TsRow* nt, uint32_t nmask,
-                                                    uint32_t* err) {
-  for (uint64_t i = (uint64_t)blockIdx.x * TS_T + threadIdx.x; i < ocap; i += (uint64_t)gridDim.x * TS_T) {
-    const TsRow o = ot[i];
-    if (o.key == KEY_EMPTY) continue;
-    bool ins;
-    const uint32_t s = ts_row_insert(nt, nmask, o.key, ins);
-    if (s == TS_NONE) {
-      atomicOr(err, TS_ERR_FULL);
-      continue;
-    }
-    nt[s].wts = o.wts;
-    nt[s].rts = o.rts;
-  }
-}
-// host-seeded rows (dcc_tso_rows_set): insert and overwrite
-__global__ __launch_bounds__(TS_T) void k_ts_rows_set(const uint64_t* keys, const uint64_t* wts,
-                                                      const uint64_t* rts, uint64_t n, TsRow* rt, uint32_t mask,
-                                                      uint32_t* cnt) {
-  uint32_t c = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * TS_T + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TS_T) {
-    bool ins;
-    const uint32_t s = ts_row_insert(rt, mask, keys[i], ins);
-    if (s == TS_NONE) {
-      atomicOr(&cnt[TS_C_ERR], TS_ERR_FULL);
-      continue;
-    }
-    c += ins;
-    rt[s].wts = wts[i];
-    rt[s].rts = rts[i];
-  }
-  ts_block_add(c, &cnt[TS_C_ROWS]);
-}
-__global__ __launch_bounds__(TS_T) void k_ts_rows_get(const uint64_t* keys, uint64_t n, const TsRow* rt,
-                                                      uint32_t mask, uint64_t* wts, uint64_t* rts) {
-  for (uint64_t i = (uint64_t)blockIdx.x * TS_T + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TS_T) {
-    const uint32_t s = ts_row_find(rt, mask, keys[i]);
-    wts[i] = s == TS_NONE ? 0 : rt[s].wts;
-    rts[i] = s == TS_NONE ? 0 : rt[s].rts;
-  }
-}
+// The persistent rows: rowtab.h's slot {key, a, b} holds a row's wts / rts
+// (tab[s].*WTS).
+using TsProbe = ProbeMix;
+constexpr auto WTS = &RowSlot::a, RTS = &RowSlot::b;
 
 // ---------------------------------------------------------------- check
 // The batch's validity before anything indexes with its offsets and before
@@ -258,9 +176,9 @@ __global__ __launch_bounds__(TS_T) void k_ts_prep(TsArgs A, KeyPack kp, uint64_t
       nwr += (uint32_t)__popcll(wb);
     }
   }
-  ts_block_add(ro, &A.cnt[TS_C_RO]);
-  __syncthreads();  // ts_block_add's LDS words are read before the next call writes them
-  ts_block_add(nwr, &A.cnt[TS_C_NWR]);
+  block_add<TS_T / 64>(ro, &A.cnt[TS_C_RO]);
+  __syncthreads();  // block_add's LDS words are read before the next call writes them
+  block_add<TS_T / 64>(nwr, &A.cnt[TS_C_NWR]);
 }
 
 // The sorted records: sk / sv are the sorted packed keys and access indices.
@@ -277,24 +195,24 @@ __global__ __launch_bounds__(TS_T) void k_ts_seg(TsArgs A, const uint64_t* __res
     s_ts[s] = (uint64_t)r.z | ((uint64_t)r.w << 32);
     heads += head;
   }
-  ts_block_add(heads, &A.cnt[TS_C_HEADS]);
+  block_add<TS_T / 64>(heads, &A.cnt[TS_C_HEADS]);
 }
 
 // The row's slot, once per segment head (the table has room for every head).
 __global__ __launch_bounds__(TS_T) void k_ts_seed(uint64_t m, const uint32_t* __restrict__ s_info,
                                                   const uint32_t* __restrict__ sv,
-                                                  const uint64_t* __restrict__ keys, TsRow* tab, uint32_t mask,
+                                                  const uint64_t* __restrict__ keys, RowSlot* tab, uint32_t mask,
                                                   uint32_t* __restrict__ hslot, uint32_t* __restrict__ cnt) {
   uint32_t c = 0;
   for (uint64_t s = (uint64_t)blockIdx.x * TS_T + threadIdx.x; s < m; s += (uint64_t)gridDim.x * TS_T) {
     if (!(s_info[s] & TS_I_HEAD)) continue;
     bool ins;
-    const uint32_t slot = ts_row_insert(tab, mask, keys[sv[s]], ins);
+    const uint32_t slot = probe_insert<TsProbe>(tab, mask, keys[sv[s]], ins);
     if (slot == TS_NONE) atomicOr(&cnt[TS_C_ERR], TS_ERR_FULL);
     hslot[s] = slot;
     c += ins;
   }
-  ts_block_add(c, &cnt[TS_C_ROWS]);
+  block_add<TS_T / 64>(c, &cnt[TS_C_ROWS]);
 }
 
 // ----------------------------------------------------------------- scan
@@ -326,7 +244,7 @@ struct ScanArgs {
   const uint32_t* sv;
   const uint32_t* hslot;
   const uint32_t* stp;
-  TsRow* tab;
+  RowSlot* tab;
   Tq* agg;          // [tiles] the tile aggregates
   Tq* pre;          // [tiles] their exclusive prefixes (k_ts_aggscan)
   uint8_t* tdone;   // [tiles] every access of the tile belongs to a decided txn
@@ -341,7 +259,7 @@ struct ScanArgs {
 // possible values equal the certain ones): rts0 and wts0 apart, as the row
 // keeps them, and the head's slot rides in `pe` to the segment's last element.
 template <bool FINAL>
-__device__ inline Tq ts_elem(uint32_t info, uint32_t st, uint64_t ts, uint32_t slot, const TsRow* tab) {
+__device__ inline Tq ts_elem(uint32_t info, uint32_t st, uint64_t ts, uint32_t slot, const RowSlot* tab) {
   const uint32_t q = info & 0xFFu, ty = (info >> 8) & 3u;
   const uint32_t state = st_state(st), p = st_prog(st);
   const bool nx = ty != DCC_XP, wr = ty == DCC_WR;
@@ -354,7 +272,7 @@ __device__ inline Tq ts_elem(uint32_t info, uint32_t st, uint64_t ts, uint32_t s
   e.f = (info & TS_I_HEAD) ? 1u : 0u;
   if (FINAL && e.f) e.pe = slot;  // TS_NONE (a full table) is reported by the last element
   if (e.f && slot != TS_NONE) {
-    const uint64_t w0 = tab[slot].wts, r0 = tab[slot].rts;
+    const uint64_t w0 = tab[slot].*WTS, r0 = tab[slot].*RTS;
     if (FINAL) {
       e.de = max(e.de, r0);
       e.dw = max(e.dw, w0);
@@ -444,8 +362,8 @@ __global__ __launch_bounds__(TS_T) void k_ts_scan(ScanArgs A) {
       if (slot == TS_NONE) {
         atomicOr(A.err, TS_ERR_STATE);
       } else {
-        A.tab[slot].wts = run.dw;
-        A.tab[slot].rts = run.de;
+        A.tab[slot].*WTS = run.dw;
+        A.tab[slot].*RTS = run.de;
       }
     }
   }
@@ -517,7 +435,7 @@ __global__ __launch_bounds__(TS_T) void k_ts_advance(TsArgs A, const uint32_t* _
       A.stp[t] = w;
     }
   }
-  ts_block_add(und_left, left_out);
+  block_add<TS_T / 64>(und_left, left_out);
 }
 
 __global__ __launch_bounds__(TS_T) void k_ts_rc(uint64_t n, const uint32_t* __restrict__ stp,
@@ -533,7 +451,7 @@ __global__ __launch_bounds__(TS_T) void k_ts_rc(uint64_t n, const uint32_t* __re
     bad |= st_state(st) == ST_UNDECIDED;
   }
   if (bad) atomicOr(&cnt[TS_C_ERR], TS_ERR_STATE);
-  ts_block_add(commits, &cnt[TS_C_COMMIT]);
+  block_add<TS_T / 64>(commits, &cnt[TS_C_COMMIT]);
 }
 
 unsigned ts_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
@@ -542,38 +460,6 @@ unsigned ts_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
 }
 
 }  // namespace
-
-// Row table capacity for `want` rows at <= 50 % load (rehash on growth).  The
-// table in use is replaced only once the new one is complete.
-int dcc_ctx::tso_rows_reserve(uint64_t want) {
-  dcc_ctx* ctx = this;
-  if (ts_bits && 2 * want <= (1ull << ts_bits)) return DCC_OK;
-  uint32_t bits = std::max<uint32_t>(ts_bits, 12);
-  while ((1ull << bits) < 2 * want) bits++;
-  if (bits > 31) return fail(DCC_ERANGE, "tso: row table exceeds 2^31 slots");
-  CR(ts_misc.ensure(this, TS_C_WORDS * 4, "tso counters"));
-  uint32_t* cnt = (uint32_t*)ts_misc.p;
-  const uint64_t cap = 1ull << bits;
-  const unsigned max_grid = (unsigned)n_cu * 16;
-  DevBuf nt;
-  CR(nt.ensure(this, cap * sizeof(TsRow), "tso row table"));
-  k_ts_clear<<<ts_grid(cap, TS_T * 4, max_grid), TS_T, 0, stream>>>((TsRow*)nt.p, cap);
-  CK(hipMemsetAsync(cnt + TS_C_ERR, 0, 4, stream));
-  if (ts_bits) {
-    const uint64_t ocap = 1ull << ts_bits;
-    k_ts_rehash<<<ts_grid(ocap, TS_T * 4, max_grid), TS_T, 0, stream>>>((const TsRow*)ts_rows.p, ocap,
-                                                                        (TsRow*)nt.p, (uint32_t)(cap - 1),
-                                                                        cnt + TS_C_ERR);
-  }
-  CK(hipGetLastError());
-  uint32_t err = 0;
-  CK(hipMemcpyAsync(&err, cnt + TS_C_ERR, 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  if (err) return fail(DCC_EIO, "tso: row table rehash failed");
-  ts_rows = std::move(nt);
-  ts_bits = bits;
-  return DCC_OK;
-}
 
 int dcc_ctx::tso_reserve(uint64_t n, uint64_t nnz, bool with_conflict) {
   const uint64_t nn = std::max<uint64_t>(n, 1), mm = std::max<uint64_t>(nnz, 1);
@@ -671,11 +557,10 @@ int dcc_ctx::tso_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_r
     CK(hipMemcpyAsync(hmisc, cnt, TS_C_RING * 4, hipMemcpyDeviceToHost, stream));
     CK(hipStreamSynchronize(stream));
     heads = ((const uint32_t*)hmisc)[TS_C_HEADS];
-    CR(tso_rows_reserve(ts_nrows + heads));
-    const uint32_t mask = (uint32_t)((1ull << ts_bits) - 1);
+    CR(ts_rows.reserve<TsProbe>(this, ts_rows.rows + heads));
     k_ts_seed<<<ts_grid(m, TS_T, max_grid), TS_T, 0, stream>>>(m, (const uint32_t*)ts_sinfo.p, vb[cur], d.keys,
-                                                               (TsRow*)ts_rows.p, mask, (uint32_t*)ts_hslot.p,
-                                                               cnt);
+                                                               (RowSlot*)ts_rows.buf.p, ts_rows.mask(),
+                                                               (uint32_t*)ts_hslot.p, cnt);
     CK(hipGetLastError());
     CK(hipMemsetAsync(ts_tdone.p, 0, tiles, stream));
     SA = ScanArgs{m,
@@ -685,7 +570,7 @@ int dcc_ctx::tso_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_r
                   vb[cur],
                   (const uint32_t*)ts_hslot.p,
                   A.stp,
-                  (TsRow*)ts_rows.p,
+                  (RowSlot*)ts_rows.buf.p,
                   (Tq*)ts_agg.p,
                   (Tq*)ts_agg.p + tiles,
                   (uint8_t*)ts_tdone.p,
@@ -749,7 +634,7 @@ int dcc_ctx::tso_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_r
   CK(hipMemcpyAsync(hmisc, cnt, TS_C_RING * 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
-  ts_nrows += hc[TS_C_ROWS];  // rows entered stay in the table whatever follows
+  ts_rows.rows += hc[TS_C_ROWS];  // rows entered stay in the table whatever follows
   if (hc[TS_C_ERR] & TS_ERR_FULL) return fail(DCC_EIO, "tso: row table full");
   if (hc[TS_C_ERR] & TS_ERR_STATE) return fail(DCC_EIO, "tso: inconsistent decisions");
   S.rounds = rounds;
@@ -773,83 +658,28 @@ extern "C" int dcc_tso_validate_epoch(dcc_ctx* ctx, const dcc_batch* batch, cons
                                       uint32_t* out_conflict, dcc_stats* out_stats) {
   if (!ctx || !batch || !out_rc || !ts) return DCC_EINVAL;
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
-  if (ctx->multi)  // the whole epoch on rank 0 (the row table is one GPU's): no collective
-    return dcc_multi_on_rank0(ctx, true, [&](dcc_ctx* s) {
-      return s->tso_epoch(batch, ts, out_rc, out_conflict, out_stats);
-    });
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  return ctx->tso_epoch(batch, ts, out_rc, out_conflict, out_stats);
+  // a multi-GPU context: the whole epoch on rank 0 (the row table is one GPU's), no collective
+  return dcc_on_device(ctx, true,
+                       [&](dcc_ctx* s) { return s->tso_epoch(batch, ts, out_rc, out_conflict, out_stats); });
 }
 
 extern "C" int dcc_tso_rows_clear(dcc_ctx* ctx) {
   if (!ctx) return DCC_EINVAL;
-  if (ctx->multi) return dcc_multi_on_rank0(ctx, false, dcc_tso_rows_clear);
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  if (ctx->ts_bits) {
-    const uint64_t cap = 1ull << ctx->ts_bits;
-    k_ts_clear<<<ts_grid(cap, TS_T * 4, (unsigned)ctx->n_cu * 16), TS_T, 0, ctx->stream>>>((TsRow*)ctx->ts_rows.p,
-                                                                                          cap);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(ctx->stream));
-  }
-  ctx->ts_nrows = 0;
-  return DCC_OK;
+  return dcc_on_device(ctx, false, [](dcc_ctx* s) { return s->ts_rows.clear(s); });
 }
 
 extern "C" int dcc_tso_rows_set(dcc_ctx* ctx, const uint64_t* keys, const uint64_t* wts, const uint64_t* rts,
                                 uint64_t n) {
   if (!ctx || (n && (!keys || !wts || !rts))) return DCC_EINVAL;
-  if (ctx->multi)
-    return dcc_multi_on_rank0(ctx, false, [&](dcc_ctx* s) { return dcc_tso_rows_set(s, keys, wts, rts, n); });
-  if (n == 0) return DCC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  for (uint64_t i = 0; i < n; i++)  // before the table changes
-    if (keys[i] == DCC_KEY_RESERVED) return ctx->fail(DCC_EINVAL, "tso rows: key equal to DCC_KEY_RESERVED");
-  CR(ctx->tso_rows_reserve(ctx->ts_nrows + n));
-  DevBuf tmp;
-  CR(tmp.ensure(ctx, n * 24, "tso seed"));
-  uint64_t* t = (uint64_t*)tmp.p;
-  uint32_t* cnt = (uint32_t*)ctx->ts_misc.p;
-  CK(hipMemsetAsync(cnt, 0, TS_C_RING * 4, ctx->stream));
-  CK(hipMemcpyAsync(t, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  CK(hipMemcpyAsync(t + n, wts, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  CK(hipMemcpyAsync(t + 2 * n, rts, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  k_ts_rows_set<<<ts_grid(n, TS_T, (unsigned)ctx->n_cu * 16), TS_T, 0, ctx->stream>>>(
-      t, t + n, t + 2 * n, n, (TsRow*)ctx->ts_rows.p, (uint32_t)((1ull << ctx->ts_bits) - 1), cnt);
-  CK(hipGetLastError());
-  uint32_t hc[TS_C_ROWS + 1];
-  CK(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, ctx->stream));
-  CK(hipStreamSynchronize(ctx->stream));
-  ctx->ts_nrows += hc[TS_C_ROWS];
-  if (hc[TS_C_ERR] & TS_ERR_FULL) return ctx->fail(DCC_EIO, "tso: row table full");
-  return DCC_OK;
+  return dcc_on_device(ctx, false, [&](dcc_ctx* s) { return s->ts_rows.set<TsProbe>(s, keys, wts, rts, n); });
 }
 
 extern "C" int dcc_tso_rows_get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* wts, uint64_t* rts, uint64_t n) {
   if (!ctx || (n && (!keys || !wts || !rts))) return DCC_EINVAL;
-  if (ctx->multi)
-    return dcc_multi_on_rank0(ctx, false, [&](dcc_ctx* s) { return dcc_tso_rows_get(s, keys, wts, rts, n); });
-  if (n == 0) return DCC_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
-  if (!ctx->ts_bits) {
-    memset(wts, 0, n * 8);
-    memset(rts, 0, n * 8);
-    return DCC_OK;
-  }
-  DevBuf tmp;
-  CR(tmp.ensure(ctx, n * 24, "tso get"));
-  uint64_t* t = (uint64_t*)tmp.p;
-  CK(hipMemcpyAsync(t, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  k_ts_rows_get<<<ts_grid(n, TS_T, (unsigned)ctx->n_cu * 16), TS_T, 0, ctx->stream>>>(
-      t, n, (const TsRow*)ctx->ts_rows.p, (uint32_t)((1ull << ctx->ts_bits) - 1), t + n, t + 2 * n);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(wts, t + n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  CK(hipMemcpyAsync(rts, t + 2 * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  CK(hipStreamSynchronize(ctx->stream));
-  return DCC_OK;
+  return dcc_on_device(ctx, false, [&](dcc_ctx* s) { return s->ts_rows.get<TsProbe>(s, keys, wts, rts, n); });
 }
 
 extern "C" uint64_t dcc_tso_rows_size(const dcc_ctx* ctx) {
-  if (ctx && ctx->multi) return dcc_multi_sub((dcc_ctx*)ctx, 0)->ts_nrows;
-  return ctx ? ctx->ts_nrows : 0;
+  if (ctx && ctx->multi) ctx = dcc_multi_sub((dcc_ctx*)ctx, 0);
+  return ctx ? ctx->ts_rows.size() : 0;
 }

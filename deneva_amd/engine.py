@@ -323,20 +323,29 @@ class Engine:
                                            C.byref(st)), self._h)
         return out_rc[:n], (out_cts[:n] if want_cts else None), st.as_dict()
 
-    def maat_rows_set(self, keys, last_read, last_write) -> None:
+    # the persistent row tables (MaaT's, TIMESTAMP's): a row's two u64 values
+    def _rows_set(self, fn, what, keys, a, b) -> None:
         keys = np.ascontiguousarray(keys, np.uint64)
-        lr = np.ascontiguousarray(last_read, np.uint64)
-        lw = np.ascontiguousarray(last_write, np.uint64)
-        _check(lib.dcc_maat_rows_set(self._h, _ptr(keys), _ptr(lr), _ptr(lw), keys.shape[0]),
-               self._h)
+        a = np.ascontiguousarray(a, np.uint64)
+        b = np.ascontiguousarray(b, np.uint64)
+        if a.shape[0] != keys.shape[0] or b.shape[0] != keys.shape[0]:
+            raise ValueError(f"{what} must have one length")
+        _check(fn(self._h, _ptr(keys), _ptr(a), _ptr(b), keys.shape[0]), self._h)
+
+    def _rows_get(self, fn, keys):
+        keys = np.ascontiguousarray(keys, np.uint64)
+        a = np.empty(keys.shape[0], np.uint64)
+        b = np.empty(keys.shape[0], np.uint64)
+        _check(fn(self._h, _ptr(keys), _ptr(a), _ptr(b), keys.shape[0]), self._h)
+        return a, b
+
+    def maat_rows_set(self, keys, last_read, last_write) -> None:
+        self._rows_set(lib.dcc_maat_rows_set, "maat_rows_set: keys, last_read and last_write",
+                       keys, last_read, last_write)
 
     def maat_rows_get(self, keys):
-        keys = np.ascontiguousarray(keys, np.uint64)
-        lr = np.empty(keys.shape[0], np.uint64)
-        lw = np.empty(keys.shape[0], np.uint64)
-        _check(lib.dcc_maat_rows_get(self._h, _ptr(keys), _ptr(lr), _ptr(lw), keys.shape[0]),
-               self._h)
-        return lr, lw
+        """(last_read u64[n], last_write u64[n]) of the rows; (0, 0) for rows never seen."""
+        return self._rows_get(lib.dcc_maat_rows_get, keys)
 
     def maat_rows_clear(self) -> None:
         _check(lib.dcc_maat_rows_clear(self._h), self._h)
@@ -537,20 +546,11 @@ class Engine:
         return out_rc[:n], (out_conflict[:n] if want_conflict else None), st.as_dict()
 
     def tso_rows_set(self, keys, wts, rts) -> None:
-        keys = np.ascontiguousarray(keys, np.uint64)
-        w = np.ascontiguousarray(wts, np.uint64)
-        r = np.ascontiguousarray(rts, np.uint64)
-        if w.shape[0] != keys.shape[0] or r.shape[0] != keys.shape[0]:
-            raise ValueError("tso_rows_set: keys, wts and rts must have one length")
-        _check(lib.dcc_tso_rows_set(self._h, _ptr(keys), _ptr(w), _ptr(r), keys.shape[0]), self._h)
+        self._rows_set(lib.dcc_tso_rows_set, "tso_rows_set: keys, wts and rts", keys, wts, rts)
 
     def tso_rows_get(self, keys):
         """(wts u64[n], rts u64[n]) of the rows; (0, 0) for rows never seen."""
-        keys = np.ascontiguousarray(keys, np.uint64)
-        w = np.empty(keys.shape[0], np.uint64)
-        r = np.empty(keys.shape[0], np.uint64)
-        _check(lib.dcc_tso_rows_get(self._h, _ptr(keys), _ptr(w), _ptr(r), keys.shape[0]), self._h)
-        return w, r
+        return self._rows_get(lib.dcc_tso_rows_get, keys)
 
     def tso_rows_clear(self) -> None:
         _check(lib.dcc_tso_rows_clear(self._h), self._h)
