@@ -29,6 +29,7 @@ RC_RCOK, RC_ABORT, RC_WAIT = 0, 2, 3  # RC, system/global.h:236
 KEY_RESERVED = 0xFFFFFFFFFFFFFFFF
 GROUP_NONE = 0xFFFFFFFF
 ACCESS_NONE = 0xFFFFFFFF
+VTS_BASE, VTS_NONE = 0, 0xFFFFFFFFFFFFFFFF  # dcc_mvcc_validate_epoch's out_vts
 DEVICE_PTRS = 0x1
 OCC_APPEND_HISTORY = 0x2
 OCC_DEFER_FINISH = 0x8
@@ -276,6 +277,14 @@ _SIGS = [
     ("dcc_tso_rows_clear", C.c_int, [_P]),
     ("dcc_tso_rows_size", C.c_uint64, [_P]),
     ("dcc_tso_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
+    ("dcc_mvcc_validate_epoch", C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, _P, C.POINTER(Stats)]),
+    ("dcc_mvcc_rows_get", C.c_int, [_P, _P, _P, _P, C.c_uint64]),
+    ("dcc_mvcc_rows_size", C.c_uint64, [_P]),
+    ("dcc_mvcc_versions_size", C.c_uint64, [_P]),
+    ("dcc_mvcc_versions_export", C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("dcc_mvcc_trim", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("dcc_mvcc_clear", C.c_int, [_P]),
+    ("dcc_mvcc_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int, C.c_int]),
     ("dcc_batch_select", C.c_int,
      [_P, C.POINTER(Batch), _P, C.c_uint8, _P, C.POINTER(SelectOut), C.POINTER(C.c_uint64),
       C.POINTER(C.c_uint64), C.POINTER(Stats)]),

@@ -501,6 +501,23 @@ struct dcc_ctx {
   int tso_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
   int tso_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* out_rc, uint32_t* out_conflict,
                 dcc_stats* st);
+  // MVCC epoch (mvcc.hip): the persistent row table {key, latest version,
+  // rts}; the version store, (key, ts) pairs sorted by (key, ts) in buffer
+  // mv_cur of two (a merge or a trim writes the other one and swaps); the
+  // epoch's versions (key, ts, txn), the late accesses, the rows' slots at the
+  // segment ends, tile offsets, the versions out of a host call.  The
+  // decisions run in the TIMESTAMP epoch's workspaces.
+  RowTab mv_rows{"mvcc"};
+  DevBuf mv_sk[2], mv_st[2];
+  int mv_cur = 0;
+  uint64_t mv_n = 0;  // versions in the store
+  DevBuf mv_ek, mv_et, mv_ex, mv_late, mv_lslot, mv_toff, mv_vts;
+  int mvcc_reserve(uint64_t n, uint64_t nnz, bool with_conflict, bool with_vts);
+  int mvcc_store_room(uint64_t need);
+  int mvcc_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* out_rc, uint32_t* out_conflict,
+                 uint64_t* out_vts, dcc_stats* st);
+  int mvcc_trim(uint64_t floor, uint64_t* n_dropped);
+  int mvcc_export(uint64_t* keys, uint64_t* ts, uint64_t cap, uint64_t* n_out);
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes

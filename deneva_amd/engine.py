@@ -559,6 +559,91 @@ class Engine:
     def tso_rows_size(self) -> int:
         return int(lib.dcc_tso_rows_size(self._h))
 
+    # ------------------------------------------------------------- MVCC
+    def mvcc_validate_epoch(self, batch: EpochBatch, ts, want_conflict: bool = True, want_vts: bool = True,
+                            out_rc=None, out_conflict=None, out_vts=None):
+        """MVCC epoch (dcc_mvcc_validate_epoch): returns (rc u8[n], conflict
+        u32[n] | None, vts u64[nnz] | None, stats).  ts as in
+        tso_validate_epoch, every value in [1, 2^64-2].  vts[a] is the
+        timestamp of the version access a read: VTS_BASE for the base row,
+        VTS_NONE for an XP access or one that was not executed (a device batch
+        gets an int64 tensor, read bit for bit).  Rows and versions persist in
+        the context (mvcc_rows_get, mvcc_versions, mvcc_trim, mvcc_clear)."""
+        n, nnz = batch.n_txn, batch.nnz
+        dev = batch.on_device
+        if ts is None:
+            ts_ptr = None
+        elif dev:
+            if not _is_device(ts):
+                raise TypeError("mvcc_validate_epoch: a device batch takes a device ts tensor")
+            ts_ptr = _ptr(ts) if n else _ptr(batch.offsets)
+        else:
+            ts = np.ascontiguousarray(ts, np.uint64)
+            ts_ptr = _ptr(ts) if n else _ptr(np.zeros(1, np.uint64))
+        if ts is not None and (_itemsize(ts) != 8 or ts.shape[0] < n):
+            raise ValueError("mvcc_validate_epoch: ts must hold n_txn 8-byte timestamps")
+        if dev:
+            import torch
+            d = batch.offsets.device
+            if out_rc is None:
+                out_rc = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
+            if want_conflict and out_conflict is None:
+                out_conflict = torch.empty(max(n, 1), dtype=torch.int32, device=d)
+            if want_vts and out_vts is None:
+                out_vts = torch.empty(max(nnz, 1), dtype=torch.int64, device=d)
+        else:
+            if out_rc is None:
+                out_rc = np.empty(max(n, 1), np.uint8)
+            if want_conflict and out_conflict is None:
+                out_conflict = np.empty(max(n, 1), np.uint32)
+            if want_vts and out_vts is None:
+                out_vts = np.empty(max(nnz, 1), np.uint64)
+        if not want_conflict:
+            out_conflict = None
+        if not want_vts:
+            out_vts = None
+        if out_rc.shape[0] < n or (out_conflict is not None and out_conflict.shape[0] < n) or \
+                (out_vts is not None and (out_vts.shape[0] < nnz or _itemsize(out_vts) != 8)):
+            raise ValueError("mvcc_validate_epoch: output buffer shorter than the epoch")
+        st = _abi.Stats()
+        b = batch.to_c()
+        _check(lib.dcc_mvcc_validate_epoch(self._h, C.byref(b), ts_ptr, _ptr(out_rc), _ptr(out_conflict),
+                                           _ptr(out_vts), C.byref(st)), self._h)
+        return (out_rc[:n], (out_conflict[:n] if want_conflict else None),
+                (out_vts[:nnz] if want_vts else None), st.as_dict())
+
+    def mvcc_rows_get(self, keys):
+        """(latest version u64[n], rts u64[n]) of the rows; (0, 0) for rows never seen."""
+        return self._rows_get(lib.dcc_mvcc_rows_get, keys)
+
+    @property
+    def mvcc_rows_size(self) -> int:
+        return int(lib.dcc_mvcc_rows_size(self._h))
+
+    @property
+    def mvcc_versions_size(self) -> int:
+        return int(lib.dcc_mvcc_versions_size(self._h))
+
+    def mvcc_versions(self):
+        """Every version in the store: (keys u64[v], ts u64[v]) sorted by (key, ts)."""
+        v = self.mvcc_versions_size
+        keys = np.empty(v, np.uint64)
+        ts = np.empty(v, np.uint64)
+        got = C.c_uint64(0)
+        _check(lib.dcc_mvcc_versions_export(self._h, _ptr(keys) if v else None, _ptr(ts) if v else None, v,
+                                            C.byref(got)), self._h)
+        return keys[:got.value], ts[:got.value]
+
+    def mvcc_trim(self, ts_floor: int) -> int:
+        """Row_mvcc::clear_history(W_REQ, ts_floor) of every row; returns the
+        number of versions dropped."""
+        dropped = C.c_uint64(0)
+        _check(lib.dcc_mvcc_trim(self._h, int(ts_floor), C.byref(dropped)), self._h)
+        return int(dropped.value)
+
+    def mvcc_clear(self) -> None:
+        _check(lib.dcc_mvcc_clear(self._h), self._h)
+
     # ------------------------------------------- select by decision (carry)
     def select_batch(self, batch: EpochBatch, rc, want: int = _abi.RC_ABORT, src=None, out=None,
                      txn_base: int = 0, nnz_base: int = 0, want_src: bool = True):
@@ -1068,6 +1153,10 @@ def nowait_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
 
 def tso_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
     return int(lib.dcc_tso_alg_bytes(n_txn, nnz, int(with_conflict)))
+
+
+def mvcc_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True, with_vts: bool = True) -> int:
+    return int(lib.dcc_mvcc_alg_bytes(n_txn, nnz, int(with_conflict), int(with_vts)))
 
 
 def select_alg_bytes(n_txn: int, n_sel: int, nnz_sel: int, n_txn_arrays: int = 0) -> int:

@@ -530,6 +530,84 @@ uint64_t dcc_tso_rows_size(const dcc_ctx* ctx);
  * [+ 4N conflict]. */
 uint64_t dcc_tso_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
 
+/* ------------------------------------------------------------------ MVCC */
+/* Epoch under CC_ALG MVCC with one txn in flight at a time, the model of the
+ * TIMESTAMP epoch above: the txns of the batch run in index order, each
+ * calling get_row for its accesses in list order (WR: P_REQ then R_REQ; RD /
+ * SCAN: R_REQ; XP: nothing) and then committing or aborting before the next
+ * txn starts, against Row_mvcc (concurrency_control/row_mvcc.cpp:198-334,
+ * storage/row.cpp:239-282, 371-390, system/txn.cpp:700-761).  ts[i] is any u64
+ * in [1, 2^64-2], in any order, ties allowed; 0 (Row_mvcc::conflict's "none",
+ * row_mvcc.cpp:208-229, and the base row below) and UINT64_MAX (DCC_VTS_NONE)
+ * are DCC_EINVAL.  In this model (DESIGN.md §8l has the argument):
+ *   R_REQ   never waits and never aborts; it returns the newest-inserted
+ *           version with wts <= ts, else the base row (:266-270), and enters
+ *           ts into the row's read history;
+ *   P_REQ   aborts iff ts < rts, the largest read timestamp of the row
+ *           (:218-239; every write timestamp is also a read timestamp, so no
+ *           write lies between ts and the next read above it);
+ *   W_REQ   (per WR access of a committed txn) installs the version ts;
+ *   XP_REQ  (per WR access of an aborted txn) drops the prewrite: the rts
+ *           bumps of an aborted txn stay, it installs no version.
+ * A txn's own writes are installed at its commit: its later reads of the row
+ * do not see them.  A row's versions are non-decreasing in ts in commit order.
+ * Per row the latest version and rts, and every version (its timestamp; row
+ * data and the writer's identity are not tracked), persist in the context
+ * across epochs.  There is no seeding call: state is reached by running
+ * epochs, which keeps rts >= latest version.
+ *   ts              [n_txn] timestamps; NULL is DCC_EINVAL
+ *   out_rc[i]       = DCC_RC_RCOK or DCC_RC_ABORT
+ *   out_conflict[i] = for an aborted txn the ordinal of the WR access that
+ *                     aborted it; DCC_ACCESS_NONE for a committed txn.  May be
+ *                     NULL.
+ *   out_vts[a]      = [nnz], batch order: the timestamp of the version access
+ *                     a's R_REQ returned (a WR that passes reports the version
+ *                     it copied); DCC_VTS_BASE for the base row; DCC_VTS_NONE
+ *                     for an XP access and for an access that was not executed
+ *                     (at or after its txn's abort ordinal).  May be NULL (no
+ *                     version is resolved then).
+ * Batch forms, DCC_DEVICE_PTRS, multi-GPU contexts (rank 0), communicators of
+ * more than one rank (DCC_ENOTSUP) and pipelined OCC epochs in flight are
+ * handled as by dcc_tso_validate_epoch.  A rejected batch (malformed offsets,
+ * a txn longer than MAX_ROW_PER_TXN, the reserved key, a ts of 0 or
+ * UINT64_MAX: DCC_EINVAL) leaves rows and versions unchanged.  An epoch that
+ * fails behind its decisions (DCC_EIO) leaves the rows' values and the
+ * versions as they were; rows the batch named may have entered the table as
+ * (0, 0), which reads as unknown.
+ * Stats: as dcc_tso_validate_epoch, except n_survivors = the accesses whose
+ * version was resolved by search (0 without out_vts) and phase_ms[3] = final
+ * pass, lookups and store merge; alg_bytes is dcc_mvcc_alg_bytes. */
+#define DCC_VTS_BASE 0ull
+#define DCC_VTS_NONE 0xFFFFFFFFFFFFFFFFull
+int dcc_mvcc_validate_epoch(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* out_rc,
+                            uint32_t* out_conflict, uint64_t* out_vts, dcc_stats* out_stats);
+/* (latest version, rts) of n rows into host arrays; a row with no version has
+ * wts 0, an unknown row is (0, 0).  dcc_mvcc_rows_size: the rows accepted
+ * batches named. */
+int dcc_mvcc_rows_get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* wts, uint64_t* rts, uint64_t n);
+uint64_t dcc_mvcc_rows_size(const dcc_ctx* ctx);
+/* The versions in the store, and all of them as (key, ts) pairs sorted by
+ * (key, ts) into host arrays of cap entries (either may be NULL); *n_out
+ * (may be NULL) = their number; cap smaller than that is DCC_ERANGE with
+ * nothing written. */
+uint64_t dcc_mvcc_versions_size(const dcc_ctx* ctx);
+int dcc_mvcc_versions_export(dcc_ctx* ctx, uint64_t* keys, uint64_t* ts, uint64_t cap, uint64_t* n_out);
+/* clear_history(W_REQ, ts_floor) (row_mvcc.cpp:42-73) of every row: a version
+ * is dropped iff the next newer version of its row also has ts < ts_floor, so
+ * the newest version below the floor stays (:308-320).  The caller guarantees
+ * that no later txn has ts < ts_floor; a read below the floor gets whatever
+ * the kept versions give.  rts is a maximum and needs no trim.  The
+ * reference's automatic trigger (whis_len > HIS_RECYCLE_LEN) is not modelled:
+ * trimming is this call.  *n_dropped may be NULL. */
+int dcc_mvcc_trim(dcc_ctx* ctx, uint64_t ts_floor, uint64_t* n_dropped);
+/* Forget rows and versions together. */
+int dcc_mvcc_clear(dcc_ctx* ctx);
+/* Algorithmic bytes of one MVCC epoch: dcc_tso_alg_bytes (the 24-B row being
+ * key, latest version, rts) [+ 8 nnz versions out].  The store's traffic
+ * (lookups, the merge of store + new versions) depends on its size and is not
+ * counted. */
+uint64_t dcc_mvcc_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict, int with_vts);
+
 /* ------------------------------ NO_WAIT lock table that lives across epochs */
 /* Row_lock's NO_WAIT state where the batches live: a device-resident map
  * row -> (lock_type, owner_cnt) that epochs acquire into and finished txns
