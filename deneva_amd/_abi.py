@@ -45,6 +45,7 @@ EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64)
 BACKOFF_REFERENCE, BACKOFF_NONE, BACKOFF_EXP = 0, 1, 2  # dcc_abortq_params.policy
 ABORTQ_SORT_FULL = 0x1
 LOCK_EX, LOCK_SH = 0, 1  # lock_t, system/global.h:289 (dcc_locktab_export)
+WD_RUN, WD_GONE = 0x10, 0x11  # rc states of the WAIT_DIE calls next to RC_RCOK / RC_WAIT / RC_ABORT
 OPT_RECHECK = 1
 OPT_BATCH_MAX = 2
 OPT_SOLVER = 5
@@ -285,6 +286,10 @@ _SIGS = [
     ("dcc_mvcc_trim", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("dcc_mvcc_clear", C.c_int, [_P]),
     ("dcc_mvcc_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int, C.c_int]),
+    ("dcc_waitdie_lock_epoch", C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, _P, C.POINTER(Stats)]),
+    ("dcc_waitdie_release", C.c_int,
+     [_P, C.POINTER(Batch), _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    ("dcc_waitdie_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
     ("dcc_batch_select", C.c_int,
      [_P, C.POINTER(Batch), _P, C.c_uint8, _P, C.POINTER(SelectOut), C.POINTER(C.c_uint64),
       C.POINTER(C.c_uint64), C.POINTER(Stats)]),

@@ -518,6 +518,20 @@ struct dcc_ctx {
                  uint64_t* out_vts, dcc_stats* st);
   int mvcc_trim(uint64_t floor, uint64_t* n_dropped);
   int mvcc_export(uint64_t* keys, uint64_t* ts, uint64_t cap, uint64_t* n_out);
+  // WAIT_DIE (waitdie.hip).  The lock state is the caller's (rc, pos) arrays;
+  // these are workspaces only: counters, txn words, the record of every
+  // access, the sorts' ping-pong pairs, the sorted records, the flag byte of
+  // every dynamic access, tile aggregates and flags; ts / rc / pos / leave and
+  // the conflict ordinals of a host call
+  DevBuf wd_misc, wd_stp, wd_arec, wd_k[2], wd_v[2], wd_stxn, wd_sinfo, wd_sts, wd_flg, wd_agg, wd_tdone;
+  DevBuf wd_hts, wd_hrc, wd_hpos, wd_hleave, wd_conf;
+  int waitdie_reserve(uint64_t n, uint64_t nnz, bool host_arrays);
+  int waitdie_stage(uint64_t n, bool dev, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
+                    const uint64_t*& ts_d, uint8_t*& rc_d, uint32_t*& pos_d, const uint8_t*& leave_d);
+  int waitdie_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, uint32_t* out_conflict,
+                    dcc_stats* st);
+  int waitdie_release(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
+                      uint64_t* out_left, uint64_t* out_promoted, dcc_stats* st);
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes

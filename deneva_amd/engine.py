@@ -559,6 +559,73 @@ class Engine:
     def tso_rows_size(self) -> int:
         return int(lib.dcc_tso_rows_size(self._h))
 
+    # --------------------------------------------------------- WAIT_DIE
+    def _waitdie_state(self, what, batch, ts, rc, pos, leave=False):
+        """Pointers of the per-txn arrays of a WAIT_DIE call, which are of the
+        batch's kind: device tensors (8 / 1 / 4-byte items, read bit for bit)
+        for a device batch, host arrays otherwise.  rc (uint8) and pos
+        (uint32) are updated in place, so a host call takes them as numpy
+        arrays of exactly those types."""
+        n = batch.n_txn
+        dev = batch.on_device
+        arrs = [("ts", ts, 8, np.uint64), ("rc", rc, 1, np.uint8), ("pos", pos, 4, np.uint32)]
+        if leave is not False:
+            arrs.append(("leave", leave, 1, np.uint8))
+        keep, ptrs = [], []
+        for name, a, size, dt in arrs:
+            if a is None:
+                ptrs.append(None)
+                continue
+            if dev:
+                if not _is_device(a):
+                    raise TypeError(f"{what}: a device batch takes a device {name} tensor")
+                if not a.is_contiguous():
+                    raise ValueError(f"{what}: {name} must be contiguous")
+            elif name in ("rc", "pos"):
+                if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags["C_CONTIGUOUS"] and
+                        a.flags["WRITEABLE"]):
+                    raise TypeError(f"{what}: {name} is updated in place: a writable contiguous {dt.__name__} array")
+            else:
+                a = np.ascontiguousarray(a, dt)
+            if _itemsize(a) != size or a.shape[0] < n:
+                raise ValueError(f"{what}: {name} must hold n_txn {size}-byte items")
+            keep.append(a)
+            ptrs.append(_ptr(a) if a.shape[0] else _ptr(batch.offsets))
+        return keep, ptrs
+
+    def waitdie_lock_epoch(self, batch: EpochBatch, ts, rc, pos, want_conflict: bool = True):
+        """WAIT_DIE acquisition epoch (dcc_waitdie_lock_epoch): the WD_RUN
+        txns request their locks from pos on.  rc and pos are updated in
+        place.  Returns (rc[:n], pos[:n], conflict u32[n] | None, stats);
+        conflict[i] is the ordinal of the request a txn waits or died at,
+        ACCESS_NONE otherwise.  Arrays are numpy for a host batch, device
+        tensors for a device batch."""
+        n = batch.n_txn
+        keep, ptrs = self._waitdie_state("waitdie_lock_epoch", batch, ts, rc, pos)
+        conf = None
+        if want_conflict:
+            if batch.on_device:
+                import torch
+                conf = torch.empty(max(n, 1), dtype=torch.int32, device=batch.offsets.device)
+            else:
+                conf = np.empty(max(n, 1), np.uint32)
+        st = _abi.Stats()
+        b = batch.to_c()
+        _check(lib.dcc_waitdie_lock_epoch(self._h, C.byref(b), *ptrs, _ptr(conf), C.byref(st)), self._h)
+        return rc[:n], pos[:n], (conf[:n] if want_conflict else None), st.as_dict()
+
+    def waitdie_release(self, batch: EpochBatch, ts, rc, pos, leave):
+        """dcc_waitdie_release: the txns with leave[i] != 0 go (WD_GONE) and
+        waiters are promoted to (WD_RUN, pos + 1); rc and pos are updated in
+        place.  Returns (n_left, n_promoted, stats)."""
+        keep, ptrs = self._waitdie_state("waitdie_release", batch, ts, rc, pos, leave)
+        st = _abi.Stats()
+        b = batch.to_c()
+        left, prom = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.dcc_waitdie_release(self._h, C.byref(b), *ptrs, C.byref(left), C.byref(prom), C.byref(st)),
+               self._h)
+        return int(left.value), int(prom.value), st.as_dict()
+
     # ------------------------------------------------------------- MVCC
     def mvcc_validate_epoch(self, batch: EpochBatch, ts, want_conflict: bool = True, want_vts: bool = True,
                             out_rc=None, out_conflict=None, out_vts=None):
@@ -1153,6 +1220,10 @@ def nowait_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
 
 def tso_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
     return int(lib.dcc_tso_alg_bytes(n_txn, nnz, int(with_conflict)))
+
+
+def waitdie_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
+    return int(lib.dcc_waitdie_alg_bytes(n_txn, nnz, int(with_conflict)))
 
 
 def mvcc_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True, with_vts: bool = True) -> int:

@@ -608,6 +608,105 @@ int dcc_mvcc_clear(dcc_ctx* ctx);
  * counted. */
 uint64_t dcc_mvcc_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict, int with_vts);
 
+/* -------------------------------------------------------------- WAIT_DIE */
+/* CC_ALG WAIT_DIE (Row_lock, concurrency_control/row_lock.cpp) as two calls:
+ * an epoch that only acquires -- it decides grant, wait or die for every
+ * request, nothing finishes inside it -- and a release the caller makes
+ * between epochs for the txns that have finished, which promotes waiters as
+ * Row_lock::lock_release does (:306-357).  When other txns finish is thereby an
+ * input, which is what gives WAIT_DIE exact semantics in epochs.
+ *
+ * State.  There is no table object: the lock state is two caller-owned per-txn
+ * arrays rc[n_txn] (u8) and pos[n_txn] (u32) over a batch the caller keeps,
+ * next to ts[n_txn], ts[i] being txn->get_timestamp() (given once, at the
+ * txn's first start, worker_thread.cpp:478): any u64, in any order, ties
+ * allowed.  RD / SCAN request LOCK_SH, every other access type LOCK_EX
+ * (row.cpp:228).  With len the txn's access count:
+ *   rc[i]         pos[i]    meaning
+ *   DCC_WD_RUN    p <= len  owns accesses [0, p); requests from p on in the
+ *                           next epoch.  A new txn is (RUN, 0).
+ *   DCC_RC_RCOK   len       owns every access
+ *   DCC_RC_WAIT   p < len   owns [0, p); queued on the row of access p
+ *   DCC_RC_ABORT  p <= len  died; still owns [0, p) until released (below)
+ *   DCC_WD_GONE   ignored   no trace
+ * "Owns access q" is one owner entry (type of q, ts[i]) on the row of q.  A
+ * row's lock_type is EX if an owner entry is EX, SH if it has owner entries
+ * and none is EX, else NONE.  Its waiter queue holds its waiter entries in
+ * descending ts, the head being the largest (:133-141); among equal ts the
+ * lower txn index is nearer the head (the reference's order there depends on
+ * arrival, and it asserts distinct owner timestamps, :107: ties are outside
+ * its domain and decided here deterministically).
+ *
+ * dcc_waitdie_lock_epoch.  The RUN txns run in index order, each calling
+ * lock_get for its accesses from pos[i] on, in list order, against the state
+ * of all non-RUN txns, the owned prefixes of the RUN txns and what the RUN
+ * txns before it left.  A request of txn i, type t, on row K:
+ *   conflict (:69-77) iff K has an EX owner entry, or t is EX and K has any
+ *   owner entry, or K has a waiter and ts_i < the largest waiter ts;
+ *   no conflict: granted, an owner entry is added (:171-196), the txn goes on;
+ *   conflict (:91-151): if ts_i > some owner's ts (the least owner ts) the txn
+ *   dies: (ABORT, its input pos), out_conflict[i] the access's ordinal; the
+ *   owner entries it gained in this epoch are released at once (system/txn.cpp
+ *   cleanup -> lock_release) and leave no trace: such a release restores the
+ *   row exactly and promotes nothing, because waiters exist only behind a head
+ *   that conflicts with lock_type.  Otherwise it waits: (WAIT, ordinal), a
+ *   waiter entry is added, out_conflict[i] the ordinal;
+ *   past its last access the txn becomes (RCOK, len), out_conflict[i]
+ *   DCC_ACCESS_NONE.
+ * A txn's own earlier entries on K count as owners like anyone else's (the
+ * reference with its asserts compiled out; :106 would trip): RD then WR of one
+ * row makes the txn wait on itself when every other owner is younger; two SH
+ * requests of one txn on one row give two entries.  Txns that are not RUN are
+ * unchanged, their out_conflict is DCC_ACCESS_NONE.
+ * Deferred cleanup: a RUN txn that dies with a carried prefix (pos > 0 on
+ * input) keeps those owner entries until the caller releases it; releasing
+ * them inside the epoch would promote waiters mid-epoch.  This is a legal
+ * interleaving of the reference, where the dying worker's cleanup is not atomic
+ * with its abort decision and other workers' lock_gets land in between.
+ *
+ * dcc_waitdie_release.  leave[i] != 0 marks the txns that go; any state may
+ * leave (the reference's waiter removal, behind assert(false) at :289-303, is
+ * what drops a WAIT txn: a caller needs it for a self-waiter or a timeout).
+ * Every entry of every leaver is removed and the leavers become GONE (their pos
+ * is left as it was).  Then :317-357 runs on each row with lock_type that of
+ * the remaining owner entries: while the queue head does not conflict with
+ * lock_type it becomes an owner and lock_type its type -- nothing, the head
+ * alone, or a leading run of SH waiters when no EX owner remains.  A promoted
+ * (WAIT, p) becomes (RUN, p + 1) (txn_table.restart_txn -> get_row_post_wait,
+ * row.cpp:313-321) and resumes in the next epoch; a RUN txn at pos == len turns
+ * RCOK there.  Releasing the leavers one at a time with lock_release, in any
+ * order, ends in the same state.  *out_left (host, may be NULL) = the leavers
+ * that were not GONE, *out_promoted (host, may be NULL) = the promoted txns.
+ * States no history reaches (two EX owners, say) are decided by these rules.
+ *
+ * rc / pos are updated in place.  With DCC_DEVICE_PTRS every array is device
+ * memory, otherwise a host array.  Compact batch forms are accepted; start_tn /
+ * finish_tn / order are ignored.  DCC_EINVAL, before rc / pos / the outputs
+ * are written: malformed offsets, the reserved key, a txn longer than
+ * MAX_ROW_PER_TXN, NULL ts / rc / pos (leave for a release), an rc byte outside
+ * the five states, pos > len, RCOK with pos != len, WAIT with pos >= len.
+ * Keys that vary in all 64 bits are DCC_ENOTSUP (the sort needs one bit next
+ * to the row).  One GPU: a dcc_init_multi context runs on rank 0; a
+ * communicator of more than one rank is DCC_ENOTSUP; pipelined OCC epochs in
+ * flight complete first.
+ * Stats of the epoch: n_commit / n_abort / n_survivors = the txns that became
+ * RCOK / ABORT / WAIT; nnz_w = EX requests (the EX accesses at or past pos of
+ * the RUN txns), n_readonly = RUN txns with none; rounds, device_ms, total_ms,
+ * alg_bytes; with profiling phase_ms: 0 = sort / build, 1 = round 1, 2 = rounds
+ * >= 2, 3 = final pass.  Stats of the release: n_commit = leavers, n_survivors
+ * = promoted, device_ms, total_ms. */
+#define DCC_WD_RUN 0x10
+#define DCC_WD_GONE 0x11
+int dcc_waitdie_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
+                           uint32_t* out_conflict /* may be NULL */, dcc_stats* out_stats);
+int dcc_waitdie_release(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
+                        const uint8_t* leave, uint64_t* out_left, uint64_t* out_promoted /* host, may be NULL */,
+                        dcc_stats* out_stats);
+/* Algorithmic bytes of one WAIT_DIE epoch: 4(N+1) offsets + 13N (ts, rc, pos
+ * in) + 9 nnz (key, type) + 24 nnz (one row aggregate per access: owner bits,
+ * least owner ts, largest waiter ts) + 5N (rc, pos out) [+ 4N conflict]. */
+uint64_t dcc_waitdie_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
+
 /* ------------------------------ NO_WAIT lock table that lives across epochs */
 /* Row_lock's NO_WAIT state where the batches live: a device-resident map
  * row -> (lock_type, owner_cnt) that epochs acquire into and finished txns
