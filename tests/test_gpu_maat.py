@@ -7,7 +7,7 @@ import pytest
 import _oracle as orc
 import deneva_amd as d
 from deneva_amd import RD, SCAN, WR, XP
-from helpers import make_batch, random_batch
+from helpers import chain_batch, make_batch, random_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +42,13 @@ def test_kat(engine):
 def test_empty_and_zero_length(engine):
     run(engine, make_batch([]))
     run(engine, make_batch([[], [(1, WR)], [], [(1, RD)]]))
+
+
+def test_chain(engine):
+    # one txn decides per round: 300 rounds, 25 batches of them, the ring of
+    # undecided counters wrapped four times
+    _, st = run(engine, chain_batch(300), literal=True)
+    assert st["rounds"] == 300
 
 
 @pytest.mark.parametrize("rw_all", [False, True])
