@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -69,6 +70,28 @@ struct RowTab {
   int set(dcc_ctx* ctx, const uint64_t* keys, const uint64_t* a, const uint64_t* b, uint64_t n);
   template <class P>
   int get(dcc_ctx* ctx, const uint64_t* keys, uint64_t* a, uint64_t* b, uint64_t n);
+};
+
+// The workspaces of a sorted-segment epoch (seg_rounds.h):
+// one set for TIMESTAMP, MVCC and WAIT_DIE, whose epochs and release use the
+// same ten arrays with the same element sizes.  Nothing in them lives across
+// calls: every call clears the counters and the tile flags it reads and
+// writes every other word before it reads it; the rows, the version store
+// and the lock state are elsewhere.  The sharing depends on that.
+struct SegWork {
+  static constexpr uint64_t TILE = 1024;    // accesses per scan tile (TS_TILE, WD_TILE)
+  static constexpr uint32_t C_WORDS = 84;   // counter words (>= TS_C_WORDS, WD_C_WORDS)
+  static constexpr size_t AGG_BYTES = 40;   // a tile aggregate (sizeof(Tq), sizeof(Wq))
+  DevBuf misc;               // counters, the ring of undecided counts
+  DevBuf stp;                // [n] txn words
+  DevBuf arec;               // [nnz] the record of every access
+  DevBuf k[2], v[2];         // the sort's ping-pong keys / values (access indices)
+  DevBuf stxn, sinfo, sts;   // sorted txns / record words / timestamps
+  DevBuf agg;                // [2 * tiles] tile aggregates, then their exclusive prefixes
+  DevBuf tdone;              // [tiles] tile flags
+  // room for n txns and nnz accesses; the per-access arrays of the sorted side
+  // in whole tiles (k_ts_scan loads 16 bytes per lane)
+  int reserve(dcc_ctx* ctx, uint64_t n, uint64_t nnz);
 };
 
 // A batch as device pointers (aliases the caller's or the ctx's staging).
@@ -491,13 +514,12 @@ struct dcc_ctx {
   int shard_groups(const uint32_t* grp, uint64_t m, uint32_t* out_dev);  // groups to batch order
   // lock tables created on this context and not yet destroyed (freed with it)
   std::vector<std::unique_ptr<dcc_locktab>> locktabs;
-  // TIMESTAMP epoch (tso.hip): the persistent row table {key, wts, rts};
-  // counters, the record of every access, txn words, the sort's
-  // ping-pong pairs, the sorted records, head slots, bounds, tile aggregates
-  // and flags, the timestamps and conflict ordinals of a host call
+  // the sorted-segment epochs' workspaces (TIMESTAMP, MVCC, WAIT_DIE)
+  SegWork seg;
+  // TIMESTAMP epoch (tso.hip): the persistent row table {key, wts, rts}; head
+  // slots, bounds, the timestamps and conflict ordinals of a host call
   RowTab ts_rows{"tso"};
-  DevBuf ts_misc, ts_arec, ts_stp, ts_k[2], ts_v[2], ts_stxn, ts_sinfo, ts_sts, ts_hslot, ts_bnd, ts_agg, ts_tdone;
-  DevBuf ts_stage, ts_conf;
+  DevBuf ts_hslot, ts_bnd, ts_stage, ts_conf;
   int tso_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
   int tso_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* out_rc, uint32_t* out_conflict,
                 dcc_stats* st);
@@ -506,7 +528,7 @@ struct dcc_ctx {
   // mv_cur of two (a merge or a trim writes the other one and swaps); the
   // epoch's versions (key, ts, txn), the late accesses, the rows' slots at the
   // segment ends, tile offsets, the versions out of a host call.  The
-  // decisions run in the TIMESTAMP epoch's workspaces.
+  // decisions run in `seg` and the TIMESTAMP epoch's workspaces.
   RowTab mv_rows{"mvcc"};
   DevBuf mv_sk[2], mv_st[2];
   int mv_cur = 0;
@@ -519,11 +541,9 @@ struct dcc_ctx {
   int mvcc_trim(uint64_t floor, uint64_t* n_dropped);
   int mvcc_export(uint64_t* keys, uint64_t* ts, uint64_t cap, uint64_t* n_out);
   // WAIT_DIE (waitdie.hip).  The lock state is the caller's (rc, pos) arrays;
-  // these are workspaces only: counters, txn words, the record of every
-  // access, the sorts' ping-pong pairs, the sorted records, the flag byte of
-  // every dynamic access, tile aggregates and flags; ts / rc / pos / leave and
-  // the conflict ordinals of a host call
-  DevBuf wd_misc, wd_stp, wd_arec, wd_k[2], wd_v[2], wd_stxn, wd_sinfo, wd_sts, wd_flg, wd_agg, wd_tdone;
+  // next to `seg` these are workspaces only: the flag byte of every dynamic
+  // access; ts / rc / pos / leave and the conflict ordinals of a host call
+  DevBuf wd_flg;
   DevBuf wd_hts, wd_hrc, wd_hpos, wd_hleave, wd_conf;
   int waitdie_reserve(uint64_t n, uint64_t nnz, bool host_arrays);
   int waitdie_stage(uint64_t n, bool dev, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
@@ -573,6 +593,13 @@ struct EpochStats {
     return DCC_OK;
   }
 };
+
+// Workgroups for `items` at `per_block` each: at least one, at most max_grid
+// (the kernels stride).
+inline unsigned launch_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
+  const uint64_t b = (items + per_block - 1) / per_block;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, max_grid));
+}
 
 // multi-GPU context (dcc_multi.cpp)
 int dcc_multi_size(const dcc_ctx* ctx);

@@ -57,6 +57,24 @@ void DevBuf::release() {
   cap = 0;
 }
 
+int SegWork::reserve(dcc_ctx* ctx, uint64_t n, uint64_t nnz) {
+  const uint64_t nn = std::max<uint64_t>(n, 1), mm = std::max<uint64_t>(nnz, 1);
+  const uint64_t tiles = (mm + TILE - 1) / TILE, mt = tiles * TILE;
+  CR(misc.ensure(ctx, C_WORDS * 4, "segment counters"));
+  CR(stp.ensure(ctx, nn * 4, "segment txn words"));
+  CR(arec.ensure(ctx, mm * 16, "segment access records"));
+  for (int q = 0; q < 2; q++) {
+    CR(k[q].ensure(ctx, mt * 8, "segment sort keys"));
+    CR(v[q].ensure(ctx, mt * 4, "segment sort values"));
+  }
+  CR(stxn.ensure(ctx, mt * 4, "segment sorted txns"));
+  CR(sinfo.ensure(ctx, mt * 4, "segment sorted records"));
+  CR(sts.ensure(ctx, mt * 8, "segment sorted timestamps"));
+  CR(agg.ensure(ctx, 2 * tiles * AGG_BYTES, "segment tile aggregates and prefixes"));
+  CR(tdone.ensure(ctx, tiles, "segment tile flags"));
+  return DCC_OK;
+}
+
 static uint64_t next_pow2(uint64_t x) {
   uint64_t p = 1;
   while (p < x) p <<= 1;

@@ -438,11 +438,6 @@ __global__ __launch_bounds__(NW_T) void k_lt_export(const LtSlot* __restrict__ t
   }
 }
 
-unsigned lt_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
-  const uint64_t b = (items + per_block - 1) / per_block;
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, max_grid));
-}
-
 }  // namespace
 
 int dcc_ctx::locktab_alloc(dcc_locktab* lt) {
@@ -461,8 +456,8 @@ int dcc_ctx::locktab_alloc(dcc_locktab* lt) {
 
 int dcc_ctx::locktab_clear(dcc_locktab* lt) {
   dcc_ctx* ctx = this;
-  k_lt_clear<<<lt_grid(lt->n_slots, NW_T * 4, (unsigned)n_cu * 16), NW_T, 0, stream>>>((LtSlot*)lt->tab[lt->cur].p,
-                                                                                      lt->n_slots);
+  k_lt_clear<<<launch_grid(lt->n_slots, NW_T * 4, (unsigned)n_cu * 16), NW_T, 0, stream>>>(
+      (LtSlot*)lt->tab[lt->cur].p, lt->n_slots);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(stream));
   lt->slots_used = lt->rows_held = lt->holds = 0;
@@ -483,7 +478,7 @@ int dcc_ctx::locktab_begin(dcc_locktab* lt, uint64_t incoming, const char* what)
       return fail(DCC_ERANGE, "lock table %s: %llu requests beside %llu held rows, room for %llu rows", what,
                   (unsigned long long)incoming, (unsigned long long)lt->rows_held, (unsigned long long)bound);
     // the held rows alone into the other buffer; the once-held ones are dropped
-    const unsigned grid = lt_grid(lt->n_slots, NW_T * 4, (unsigned)n_cu * 16);
+    const unsigned grid = launch_grid(lt->n_slots, NW_T * 4, (unsigned)n_cu * 16);
     LtSlot* to = (LtSlot*)lt->tab[lt->cur ^ 1].p;
     k_lt_clear<<<grid, NW_T, 0, stream>>>(to, lt->n_slots);
     k_lt_rebuild<<<grid, NW_T, 0, stream>>>((const LtSlot*)lt->tab[lt->cur].p, lt->n_slots, to,
@@ -514,7 +509,7 @@ int dcc_ctx::locktab_grant(dcc_locktab* lt, const LtEpoch& E) {
   LtGrant A{E.n, E.off, E.keys, E.at, E.state, E.lp, E.err, (LtSlot*)lt->tab[lt->cur].p, (uint32_t)(lt->n_slots - 1),
             ctl};
   // fewer, longer workgroups than the epoch's passes: the combiner folds what one workgroup sees
-  k_lt_grant<<<lt_grid(E.n, NW_T >> E.lp, (unsigned)n_cu * 4), NW_T, 0, stream>>>(A);
+  k_lt_grant<<<launch_grid(E.n, NW_T >> E.lp, (unsigned)n_cu * 4), NW_T, 0, stream>>>(A);
   CK(hipGetLastError());
   CK(hipMemcpyAsync((uint8_t*)hmisc + LT_HMISC_OFF, ctl, LT_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
   return DCC_OK;
@@ -559,7 +554,7 @@ int dcc_ctx::locktab_acquire(dcc_locktab* lt, const dcc_calvin_held* rows, bool 
   if (prof) CK(hipEventRecord(pev[0], stream));
   CR(locktab_begin(lt, n, "acquire"));
   uint32_t* ctl = (uint32_t*)lt->ctl.p;
-  const unsigned grid = lt_grid(n, NW_T, (unsigned)n_cu * 16);
+  const unsigned grid = launch_grid(n, NW_T, (unsigned)n_cu * 16);
   k_lt_keys<<<grid, NW_T, 0, stream>>>(hk, n, ctl);  // a reserved key: nothing is acquired
   LtEpoch E;
   E.n = n;
@@ -621,13 +616,13 @@ int dcc_ctx::locktab_release(dcc_locktab* lt, const dcc_batch* b, const uint8_t*
   A.sid = (uint32_t*)nw_sid.p;
   A.ctl = ctl;
   const unsigned max_grid = (unsigned)n_cu * 16;
-  const unsigned grid = lt_grid(A.n, NW_T >> A.lp, max_grid);
-  const unsigned grid_c = lt_grid(A.n, NW_T >> A.lp, (unsigned)n_cu * 4);  // the passes with a combiner
+  const unsigned grid = launch_grid(A.n, NW_T >> A.lp, max_grid);
+  const unsigned grid_c = launch_grid(A.n, NW_T >> A.lp, (unsigned)n_cu * 4);  // the passes with a combiner
   const bool prof = profiling;
   CK(hipMemsetAsync(ctl, 0, LT_C_WORDS * 4, stream));
   CK(hipEventRecord(ev0, stream));
   if (prof) CK(hipEventRecord(pev[0], stream));
-  if (A.off) k_lt_rcheck<<<lt_grid(A.n, NW_T * 4, max_grid), NW_T, 0, stream>>>(A.off, A.n, A.nnz, ctl);
+  if (A.off) k_lt_rcheck<<<launch_grid(A.n, NW_T * 4, max_grid), NW_T, 0, stream>>>(A.off, A.n, A.nnz, ctl);
   if (prof) CK(hipEventRecord(pev[1], stream));
   k_lt_radd<<<grid_c, NW_T, 0, stream>>>(A);
   if (prof) CK(hipEventRecord(pev[2], stream));
@@ -675,7 +670,7 @@ int dcc_ctx::locktab_export(dcc_locktab* lt, uint64_t* keys, uint8_t* lock_type,
   uint32_t* ctl = (uint32_t*)lt->ctl.p;
   CK(hipMemsetAsync(ctl, 0, LT_C_WORDS * 4, stream));
   // rows <= cap_rows, the size of the staging arrays
-  k_lt_export<<<lt_grid(lt->n_slots, NW_T * 4, (unsigned)n_cu * 16), NW_T, 0, stream>>>(
+  k_lt_export<<<launch_grid(lt->n_slots, NW_T * 4, (unsigned)n_cu * 16), NW_T, 0, stream>>>(
       (const LtSlot*)lt->tab[lt->cur].p, lt->n_slots, dk, dt, dc, rows, ctl);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(hmisc, ctl, LT_C_WORDS * 4, hipMemcpyDeviceToHost, stream));

@@ -72,7 +72,7 @@ constexpr uint32_t TS_ITEMS = 4;                  // consecutive sorted accesses
 
 namespace {
 
-// engine counter words (ts_misc): late accesses; the epoch's versions (u64)
+// engine counter words (next to tso_kernels.h's): late accesses; the epoch's versions (u64)
 constexpr uint32_t MV_C_NLATE = TS_C_ENGINE, MV_C_NC = TS_C_ENGINE + 2;
 constexpr uint32_t MV_OFF_T = 1024;  // threads of the tile-offset scan
 
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(TS_T) void k_mv_tscheck(const uint64_t* __restrict_
     const uint64_t v = ts[t];
     bad |= v == 0 || v == ~0ull;
   }
-  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(&cnt[TS_C_ERR], TS_ERR_TS);
+  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(&cnt[SEG_C_ERR], TS_ERR_TS);
 }
 
 // ----------------------------------------------------- the epoch's versions
@@ -346,7 +346,7 @@ int dcc_ctx::mvcc_store_room(uint64_t need) {
 int dcc_ctx::mvcc_reserve(uint64_t n, uint64_t nnz, bool with_conflict, bool with_vts) {
   const uint64_t mm = std::max<uint64_t>(nnz, 1);
   const uint64_t mt = (mm + TS_TILE - 1) / TS_TILE * TS_TILE;
-  CR(tso_reserve(n, nnz, with_conflict));  // the decisions run in the TIMESTAMP engine's workspaces
+  CR(tso_reserve(n, nnz, with_conflict));  // the decisions run in the TIMESTAMP epoch's workspaces
   CR(mv_ek.ensure(this, mt * 8, "mvcc epoch version keys"));
   CR(mv_et.ensure(this, mt * 8, "mvcc epoch version timestamps"));
   CR(mv_ex.ensure(this, mt * 4, "mvcc epoch version txns"));
@@ -364,7 +364,7 @@ int dcc_ctx::mvcc_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_
   dcc_stats& S = es.S;
   if (!out_rc) return fail(DCC_EINVAL, "mvcc: null out_rc");
   if (!ts_in) return fail(DCC_EINVAL, "mvcc: null ts");
-  CR(check_batch(b, false));  // the offsets are checked on the device (k_ts_check)
+  CR(check_batch(b, false));  // the offsets are checked on the device (k_batch_check)
   if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "mvcc: single-GPU engine");
   const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
   if (b->n_txn == 0) {
@@ -386,7 +386,7 @@ int dcc_ctx::mvcc_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_
   CR(ts_build<Mv>(
       this, mv_rows, d, ts_dev, R,
       [&](uint32_t* cnt) {
-        k_mv_tscheck<<<ts_grid(n, TS_T * 4, (unsigned)n_cu * 16), TS_T, 0, stream>>>(ts_dev, n, cnt);
+        k_mv_tscheck<<<launch_grid(n, TS_T * 4, (unsigned)n_cu * 16), TS_T, 0, stream>>>(ts_dev, n, cnt);
         CK(hipGetLastError());
         return (int)DCC_OK;
       },
@@ -414,7 +414,7 @@ int dcc_ctx::mvcc_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_
     // every txn decided: versions by the fast path, the late list, the rows' new values
     const MvScanArgs SA = scan(R.SA);
     k_ts_scan<false, true, Mv><<<(unsigned)tiles, TS_T, 0, stream>>>(SA);
-    k_ts_aggscan<<<1, TS_AGG_T, 0, stream>>>(SA.agg, SA.pre, tiles, nullptr, nullptr);
+    k_tile_aggscan<TqOp><<<1, SEG_AGG_T, 0, stream>>>(SA.agg, SA.pre, tiles, nullptr, nullptr);
     k_ts_scan<true, true, Mv><<<(unsigned)tiles, TS_T, 0, stream>>>(SA);
     // the epoch's versions in (row, index) order
     uint64_t* toff = (uint64_t*)mv_toff.p;
@@ -427,15 +427,15 @@ int dcc_ctx::mvcc_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_
     k_mv_commits<true><<<(unsigned)tiles, TS_T, 0, stream>>>(m, SA.s_info, SA.s_txn, SA.s_ts, SA.sv, SA.stp,
                                                              d.keys, toff, ek, et, ex);
     if (vts_dev)
-      k_mv_lookup<<<ts_grid(m, TS_T, max_grid), TS_T, 0, stream>>>(SA.late, SA.nlate, d.keys, A.arec, ek, et, ex,
-                                                                   nc_dev, old, vts_dev);
+      k_mv_lookup<<<launch_grid(m, TS_T, max_grid), TS_T, 0, stream>>>(SA.late, SA.nlate, d.keys, A.arec, ek, et, ex,
+                                                                       nc_dev, old, vts_dev);
     if (R.nnz_w)  // an epoch without a WR access installs nothing: the store stays where it is
-      k_mv_merge<<<ts_grid(mv_n + R.nnz_w, TS_T, max_grid), TS_T, 0, stream>>>(
+      k_mv_merge<<<launch_grid(mv_n + R.nnz_w, TS_T, max_grid), TS_T, 0, stream>>>(
           old, ek, et, nc_dev, (uint64_t*)mv_sk[mv_cur ^ 1].p, (uint64_t*)mv_st[mv_cur ^ 1].p);
-    k_mv_rows<<<ts_grid(m, TS_T, max_grid), TS_T, 0, stream>>>(m, SA.s_info, SA.lslot, SA.rowv, SA.tab,
-                                                               &cnt[TS_C_ERR]);
+    k_mv_rows<<<launch_grid(m, TS_T, max_grid), TS_T, 0, stream>>>(m, SA.s_info, SA.lslot, SA.rowv, SA.tab,
+                                                                   &cnt[SEG_C_ERR]);
   }
-  k_ts_rc<<<ts_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, A.stp, rc_dev, conf_dev, cnt);
+  k_ts_rc<<<launch_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, A.stp, rc_dev, conf_dev, cnt);
   CK(hipGetLastError());
   if (prof) CK(hipEventRecord(pev[4], stream));
   CK(hipEventRecord(ev1, stream));
@@ -448,8 +448,8 @@ int dcc_ctx::mvcc_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
   mv_rows.rows += hc[TS_C_ROWS];  // rows entered stay in the table whatever follows
-  if (hc[TS_C_ERR] & TS_ERR_FULL) return fail(DCC_EIO, "mvcc: row table full");
-  if (hc[TS_C_ERR] & TS_ERR_STATE) return fail(DCC_EIO, "mvcc: inconsistent decisions");
+  if (hc[SEG_C_ERR] & TS_ERR_FULL) return fail(DCC_EIO, "mvcc: row table full");
+  if (hc[SEG_C_ERR] & TS_ERR_STATE) return fail(DCC_EIO, "mvcc: inconsistent decisions");
   uint64_t nc;
   memcpy(&nc, hc + MV_C_NC, 8);
   if (nc) {  // the merged store is the store (an epoch without a commit leaves it where it is)

@@ -26,7 +26,8 @@
 // longest txn), one access per lane, so adjacent lanes load adjacent
 // accesses; per-txn reductions are ballots masked to the txn's lanes.
 //
-// Kernels:  k_nw_check   offsets / reserved keys / longest txn
+// Kernels (the batch check and the rounds loop are seg_rounds.h's, DESIGN.md
+// §8n):
 //           k_nw_held    held rows into the table (tag-0 words)
 //           k_nw_build   every requested key into the table, the slot id of
 //                        every request, self-conflicts decided, round-1 words
@@ -46,17 +47,17 @@
 #include "dcc_device.h"
 #include "nowait_lanes.h"
 #include "occ_kernels.h"
+#include "seg_rounds.h"
 
 using namespace dcc;
 
 namespace {
 
-constexpr uint32_t NW_RING = 64;      // list-length ring (> the rounds of one host batch)
 constexpr uint32_t NW_STAGE = 1024;   // blocked txns a workgroup stages before one list append
-constexpr uint32_t NW_ERR_OFF = 1, NW_ERR_KEY = 2, NW_ERR_FULL = 4, NW_ERR_STATE = 8;
-// counter words (nw_misc)
-constexpr uint32_t NW_C_ERR = 0, NW_C_MAXLEN = 1, NW_C_NEX = 2, NW_C_RO = 3, NW_C_COMMIT = 4,
-                   NW_C_RING = 8, NW_C_WORDS = NW_C_RING + NW_RING;
+// error bits next to CHK_ERR_* (a held key sets CHK_ERR_KEY too)
+constexpr uint32_t NW_ERR_FULL = 4, NW_ERR_STATE = 8;
+// counter words (nw_misc) next to SEG_C_ERR / SEG_C_MAXLEN; the ring holds the list lengths
+constexpr uint32_t NW_C_NEX = 2, NW_C_RO = 3, NW_C_COMMIT = 4, NW_C_RING = 8, NW_C_WORDS = NW_C_RING + SEG_RING;
 
 // A txn names a row twice with EX on either side (NO_WAIT keeps no owner
 // list, row_lock.cpp:176-182): the lanes of the later requests.  Rows compare
@@ -73,35 +74,6 @@ __device__ inline bool self_conflict(const Seg& g, uint32_t lp, bool v, uint32_t
   return sc;
 }
 
-__global__ __launch_bounds__(NW_T) void k_nw_check(const uint32_t* __restrict__ off, uint64_t n,
-                                                   const uint64_t* __restrict__ keys, uint64_t nnz,
-                                                   uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t s_len, s_err;
-  if (threadIdx.x == 0) {
-    s_len = 0;
-    s_err = 0;
-  }
-  __syncthreads();
-  uint32_t len = 0, err = 0;
-  const uint64_t tid = (uint64_t)blockIdx.x * NW_T + threadIdx.x, stride = (uint64_t)gridDim.x * NW_T;
-  for (uint64_t t = tid; t < n; t += stride) {
-    const uint32_t a0 = off[t], b0 = off[t + 1];
-    if (b0 < a0) err |= NW_ERR_OFF;
-    else len = max(len, b0 - a0);
-    if (t == 0 && a0 != 0) err |= NW_ERR_OFF;
-    if (t == n - 1 && b0 != nnz) err |= NW_ERR_OFF;
-  }
-  for (uint64_t x = tid; x < nnz; x += stride)
-    if (keys[x] == KEY_EMPTY) err |= NW_ERR_KEY;
-  if (len) atomicMax(&s_len, len);
-  if (err) atomicOr(&s_err, err);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_len) atomicMax(&cnt[NW_C_MAXLEN], s_len);
-    if (s_err) atomicOr(&cnt[NW_C_ERR], s_err);
-  }
-}
-
 __global__ __launch_bounds__(NW_T) void k_nw_held(const uint64_t* __restrict__ keys,
                                                   const uint8_t* __restrict__ at, uint64_t n, Slot* tab,
                                                   uint32_t mask, uint32_t* __restrict__ cnt) {
@@ -109,12 +81,12 @@ __global__ __launch_bounds__(NW_T) void k_nw_held(const uint64_t* __restrict__ k
   for (uint64_t x = (uint64_t)blockIdx.x * NW_T + threadIdx.x; x < n; x += stride) {
     const uint64_t key = keys[x];
     if (key == KEY_EMPTY) {
-      atomicOr(&cnt[NW_C_ERR], NW_ERR_KEY);
+      atomicOr(&cnt[SEG_C_ERR], CHK_ERR_KEY);
       continue;
     }
     const uint32_t s = table_insert(tab, mask, key);
     if (s == SID_NONE) {
-      atomicOr(&cnt[NW_C_ERR], NW_ERR_FULL);
+      atomicOr(&cnt[SEG_C_ERR], NW_ERR_FULL);
       continue;
     }
     own_min(&tab[s].own, 0u);  // committed word below every txn
@@ -160,7 +132,7 @@ __global__ __launch_bounds__(NW_T) void k_nw_build(NwArgs A) {
       ex = is_ex(A.at[x]);
       s = table_insert(A.tab, A.mask, A.keys[x]);
       A.sid[x] = s;
-      if (s == SID_NONE) atomicOr(&A.cnt[NW_C_ERR], NW_ERR_FULL);
+      if (s == SID_NONE) atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_FULL);
     }
     const bool sc = self_conflict(g, A.lp, v, s, ex);
     const bool selfc = (ballot64(sc) & g.mask) != 0;
@@ -307,7 +279,7 @@ __global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict
     if (tv && g.a == 0) {
       rc[t] = st == ST_COMMIT ? DCC_RC_RCOK : DCC_RC_ABORT;
       commits += st == ST_COMMIT ? 1u : 0u;
-      if (st == ST_UNDECIDED) atomicOr(&A.cnt[NW_C_ERR], NW_ERR_STATE);
+      if (st == ST_UNDECIDED) atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_STATE);
     }
     if (!conflict) continue;
     if (!ballot64(ab)) {  // no aborted txn in the wave
@@ -337,7 +309,7 @@ __global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict
       uint32_t o = DCC_ACCESS_NONE;
       if (ab) {
         if (cb) o = (uint32_t)__builtin_ctzll(cb) - g.seg0;
-        else atomicOr(&A.cnt[NW_C_ERR], NW_ERR_STATE);  // aborted without a conflicting request
+        else atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_STATE);  // aborted without a conflicting request
       }
       conflict[t] = o;
     }
@@ -345,11 +317,6 @@ __global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict
   if (commits) atomicAdd(&s_commit, commits);
   __syncthreads();
   if (threadIdx.x == 0 && s_commit) atomicAdd(&A.cnt[NW_C_COMMIT], s_commit);
-}
-
-unsigned nw_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
-  const uint64_t b = (items + per_block - 1) / per_block;
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, max_grid));
 }
 
 }  // namespace
@@ -371,7 +338,7 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   EpochStats es;
   dcc_stats& S = es.S;
   if (!out_rc) return fail(DCC_EINVAL, "nowait: null out_rc");
-  CR(check_batch(b, false));  // the offsets are checked on the device (k_nw_check)
+  CR(check_batch(b, false));  // the offsets are checked on the device (k_batch_check)
   if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "nowait: single-GPU engine");
   const uint64_t hn = held ? held->n : 0;
   if (lt && hn) return fail(DCC_EINVAL, "nowait: a held list next to a lock table");
@@ -400,21 +367,14 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
 
   // reject a malformed batch before anything indexes with its offsets
   CK(hipMemsetAsync(cnt, 0, NW_C_WORDS * 4, stream));
-  k_nw_check<<<nw_grid(std::max(n, m), NW_T * 4, max_grid), NW_T, 0, stream>>>(d.off, n, d.keys, m, cnt);
+  k_batch_check<false><<<launch_grid(std::max(n, m), CHK_T * 4, max_grid), CHK_T, 0, stream>>>(
+      d.off, n, d.keys, m, cnt);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(hmisc, cnt, 8, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
-  uint32_t maxlen = 0;
-  {
-    const uint32_t* hc = (const uint32_t*)hmisc;
-    if (hc[NW_C_ERR] & NW_ERR_OFF) return fail(DCC_EINVAL, "batch: malformed offsets");
-    if (hc[NW_C_ERR] & NW_ERR_KEY) return fail(DCC_EINVAL, "batch: key equal to DCC_KEY_RESERVED");
-    maxlen = hc[NW_C_MAXLEN];
-    if (maxlen > MAX_TXN_LEN)
-      return fail(DCC_EINVAL, "batch: a txn has %u accesses (> MAX_ROW_PER_TXN=%u)", maxlen, MAX_TXN_LEN);
-  }
-  uint32_t lp = 0;
-  while ((1u << lp) < maxlen) lp++;
+  BatchShape shape;
+  CR(batch_checked(this, (const uint32_t*)hmisc, m, false, shape));
+  const uint32_t lp = shape.lp;
   const uint64_t per_block = NW_T >> lp;  // txns per workgroup step
 
   const bool prof = profiling;
@@ -427,10 +387,10 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
     const uint64_t* hk;
     const uint8_t* ha;
     CR(stage_held(held, dev, hk, ha));
-    k_nw_held<<<nw_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt);
+    k_nw_held<<<launch_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt);
   }
   NwArgs A{n, d.off, d.keys, d.acctype, tab, mask, lp, (uint32_t*)nw_sid.p, (uint8_t*)state.p, cnt};
-  k_nw_build<<<nw_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
+  k_nw_build<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
   CK(hipGetLastError());
   // the table's held rows take the place of a held list: their tag-0 words
   LtEpoch L;
@@ -443,55 +403,32 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
     L.state = A.state;
     L.tab = tab;
     L.lp = lp;
-    L.err = &cnt[NW_C_ERR];
-    L.grid = nw_grid(n, per_block, max_grid);
+    L.err = &cnt[SEG_C_ERR];
+    L.grid = launch_grid(n, per_block, max_grid);
     CR(locktab_seed(lt, L));
   }
   if (prof) CK(hipEventRecord(pev[1], stream));
 
-  // ---- rounds: decide(r) reads its list length from ring[r % NW_RING] and
-  // appends the blocked txns to ring[(r + 1) % NW_RING], which publish(r)
-  // cleared (the whole ring is clear before round 1).  Several rounds are
-  // enqueued between host synchronisations; rounds past the fixed point find
-  // empty lists.
-  uint32_t r = 1, rounds = 0;
-  uint64_t m_bound = n;
-  uint32_t batch = std::min<uint32_t>(2, batch_max);
-  bool done = false;
-  while (!done) {
-    const uint32_t r0 = r;
-    for (uint32_t q = 0; q < batch; q++, r++) {
-      const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;  // tags 62 .. 1, then again
-      const uint32_t tag = round_tag(er);
-      const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
-      const uint32_t* min_ = &ring[r % NW_RING];
-      const unsigned grid = nw_grid(m_bound, per_block, max_grid);
-      if (r > 1) {
-        if (er == 1)  // tag space exhausted: drop the tagged words, every undecided txn republishes
-          k_nw_retag<<<nw_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
-        k_nw_publish<<<grid, NW_T, 0, stream>>>(A, tag, lin, min_, &ring[(r + 1) % NW_RING]);
-      }
-      k_nw_decide<<<grid, NW_T, 0, stream>>>(A, tag, lin, min_, lists[(r + 1) & 1], &ring[(r + 1) % NW_RING]);
-      if (prof && r == 1) CK(hipEventRecord(pev[2], stream));
-    }
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(hmisc, ring, NW_RING * 4, hipMemcpyDeviceToHost, stream));
-    CK(hipStreamSynchronize(stream));
-    const uint32_t* hr = (const uint32_t*)hmisc;
-    for (uint32_t q = r0; q < r; q++) {
-      const uint32_t left = hr[(q + 1) % NW_RING];
-      if (left == 0) {
-        rounds = q;
-        done = true;
-        break;
-      }
-      m_bound = left;
-    }
-    if (!done && r > n + 2) return fail(DCC_EIO, "nowait: fixed point did not converge");
-    batch = std::min<uint32_t>(batch * 2, std::min<uint32_t>(batch_max, NW_RING / 2));
-  }
-  if (prof) CK(hipEventRecord(pev[3], stream));
-  k_nw_final<<<nw_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
+  // ---- rounds (seg_rounds.h's loop): decide(r) reads its list length `left`
+  // and appends the blocked txns to the list whose length word publish(r)
+  // cleared (the whole ring is clear before round 1, which takes every txn and
+  // clears nothing).  Rounds past the fixed point find empty lists.  `bound`
+  // sizes the grids.
+  uint32_t rounds = 0;
+  CR(rounds_loop(this, ring, n, n + 2, "nowait", rounds,
+                 [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
+                   const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;  // tags 62 .. 1, then again
+                   const uint32_t tag = round_tag(er);
+                   const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
+                   const unsigned grid = launch_grid(bound, per_block, max_grid);
+                   if (r > 1) {
+                     if (er == 1)  // tag space exhausted: drop the tagged words, every undecided txn republishes
+                       k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
+                     k_nw_publish<<<grid, NW_T, 0, stream>>>(A, tag, lin, left, left_out);
+                   }
+                   k_nw_decide<<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
+                 }));
+  k_nw_final<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
   CK(hipGetLastError());
   if (lt) CR(locktab_grant(lt, L));  // the committed txns' requests stay in the table
   if (prof) CK(hipEventRecord(pev[4], stream));
@@ -503,9 +440,9 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   CK(hipMemcpyAsync(hmisc, cnt, NW_C_RING * 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
-  if (hc[NW_C_ERR] & NW_ERR_KEY) return fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
-  if (hc[NW_C_ERR] & NW_ERR_FULL) return fail(DCC_EIO, "nowait: lock table full");
-  if (hc[NW_C_ERR] & NW_ERR_STATE) return fail(DCC_EIO, "nowait: inconsistent decisions");
+  if (hc[SEG_C_ERR] & CHK_ERR_KEY) return fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
+  if (hc[SEG_C_ERR] & NW_ERR_FULL) return fail(DCC_EIO, "nowait: lock table full");
+  if (hc[SEG_C_ERR] & NW_ERR_STATE) return fail(DCC_EIO, "nowait: inconsistent decisions");
   S.rounds = rounds;
   S.n_commit = hc[NW_C_COMMIT];
   S.n_abort = n - hc[NW_C_COMMIT];

@@ -36,15 +36,14 @@
 // possible sets only shrink, and for the lowest undecided txn the two are
 // equal, so it is decided in every round: the result is the replay's.
 //
-// Kernels (tso_kernels.h, shared with the MVCC engine of mvcc.hip):
-//           k_ts_check    offsets / reserved keys / longest txn / varying key bits
+// Kernels (tso_kernels.h, shared with the MVCC engine of mvcc.hip; the batch
+// check, k_tile_aggscan and the rounds loop are seg_rounds.h's):
 //           k_ts_prep     packed sort keys, the record of every access, WR / read-only counts
 //           k_ts_seg      sorted records (txn, position | type | head | last, ts), heads
 //           k_ts_seed     a row-table slot per segment head (find or insert)
 //           k_ts_scan     per 1,024-access tile: its aggregate (reduce) or,
 //                         behind the scanned aggregates, the bounds of every
 //                         access (apply); the final apply writes the rows
-//           k_ts_aggscan  exclusive scan of the tile aggregates (one workgroup)
 //           k_ts_advance  one round of decisions from the bounds
 //           k_ts_rc       RC bytes, conflict ordinals, the commit count
 // No workgroup waits on another: a round is reduce / scan of aggregates /
@@ -81,20 +80,9 @@ struct Tso {
 int dcc_ctx::tso_reserve(uint64_t n, uint64_t nnz, bool with_conflict) {
   const uint64_t nn = std::max<uint64_t>(n, 1), mm = std::max<uint64_t>(nnz, 1);
   const uint64_t mt = (mm + TS_TILE - 1) / TS_TILE * TS_TILE;  // whole tiles: 16-B loads
-  CR(ts_misc.ensure(this, TS_C_WORDS * 4, "tso counters"));
-  CR(ts_stp.ensure(this, nn * 4, "tso txn words"));
-  CR(ts_arec.ensure(this, mm * 16, "tso access records"));
-  for (int q = 0; q < 2; q++) {
-    CR(ts_k[q].ensure(this, mt * 8, "tso sort keys"));
-    CR(ts_v[q].ensure(this, mt * 4, "tso sort values"));
-  }
-  CR(ts_stxn.ensure(this, mt * 4, "tso sorted txns"));
-  CR(ts_sinfo.ensure(this, mt * 4, "tso sorted records"));
-  CR(ts_sts.ensure(this, mt * 8, "tso sorted timestamps"));
+  CR(seg.reserve(this, n, nnz));
   CR(ts_hslot.ensure(this, mt * 4, "tso head slots"));
   CR(ts_bnd.ensure(this, mm * 16, "tso bounds"));
-  CR(ts_agg.ensure(this, 2 * (mt / TS_TILE) * sizeof(Tq), "tso tile aggregates and prefixes"));
-  CR(ts_tdone.ensure(this, mt / TS_TILE, "tso tile flags"));
   CR(cv_scratch.ensure(this, rs_scratch_words(mm) * 4 + 64, "radix scratch"));
   CR(rc.ensure(this, n + 16, "rc"));
   if (with_conflict) CR(ts_conf.ensure(this, nn * 4, "tso conflicts"));
@@ -108,7 +96,7 @@ int dcc_ctx::tso_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_r
   dcc_stats& S = es.S;
   if (!out_rc) return fail(DCC_EINVAL, "tso: null out_rc");
   if (!ts_in) return fail(DCC_EINVAL, "tso: null ts");
-  CR(check_batch(b, false));  // the offsets are checked on the device (k_ts_check)
+  CR(check_batch(b, false));  // the offsets are checked on the device (k_batch_check)
   if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "tso: single-GPU engine");
   const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
   if (b->n_txn == 0) {
@@ -135,10 +123,10 @@ int dcc_ctx::tso_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_r
   const unsigned max_grid = R.max_grid;
   if (m) {  // every txn decided: the rows' new state from each segment's last element
     k_ts_scan<false, true, Tso><<<(unsigned)tiles, TS_T, 0, stream>>>(SA);
-    k_ts_aggscan<<<1, TS_AGG_T, 0, stream>>>(SA.agg, SA.pre, tiles, nullptr, nullptr);
+    k_tile_aggscan<TqOp><<<1, SEG_AGG_T, 0, stream>>>(SA.agg, SA.pre, tiles, nullptr, nullptr);
     k_ts_scan<true, true, Tso><<<(unsigned)tiles, TS_T, 0, stream>>>(SA);
   }
-  k_ts_rc<<<ts_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, A.stp, rc_dev, conf_dev, cnt);
+  k_ts_rc<<<launch_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, A.stp, rc_dev, conf_dev, cnt);
   CK(hipGetLastError());
   if (prof) CK(hipEventRecord(pev[4], stream));
   CK(hipEventRecord(ev1, stream));
@@ -150,8 +138,8 @@ int dcc_ctx::tso_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_r
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
   ts_rows.rows += hc[TS_C_ROWS];  // rows entered stay in the table whatever follows
-  if (hc[TS_C_ERR] & TS_ERR_FULL) return fail(DCC_EIO, "tso: row table full");
-  if (hc[TS_C_ERR] & TS_ERR_STATE) return fail(DCC_EIO, "tso: inconsistent decisions");
+  if (hc[SEG_C_ERR] & TS_ERR_FULL) return fail(DCC_EIO, "tso: row table full");
+  if (hc[SEG_C_ERR] & TS_ERR_STATE) return fail(DCC_EIO, "tso: inconsistent decisions");
   S.rounds = R.rounds;
   S.n_commit = hc[TS_C_COMMIT];
   S.n_abort = n - hc[TS_C_COMMIT];

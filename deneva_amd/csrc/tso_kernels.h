@@ -1,7 +1,8 @@
 // The timestamp-ordering epoch that TIMESTAMP (tso.hip) and MVCC (mvcc.hip)
-// share: the validity check, the sort by row, the sorted records, the rounds
-// fixed point over segmented prefix maxima and the final pass (tso.hip's head
-// comment has the algorithm).  What both engines run unchanged is written once
+// share: the sort by row, the sorted records, a round of the fixed point over
+// segmented prefix maxima and the final pass (tso.hip's head comment has the
+// algorithm; the batch check, the aggregate scan and the rounds loop are
+// seg_rounds.h's).  What both engines run unchanged is written once
 // here; what differs is an engine type E:
 //
 //   E::MVCC   false  TIMESTAMP: a RD / SCAN meets the committed-writer bound,
@@ -32,19 +33,18 @@
 #include "occ_kernels.h"
 #include "radix_sort.h"
 #include "rowtab.h"
+#include "seg_rounds.h"
 
 namespace dcc {
 namespace {
 
 constexpr uint32_t TS_TILE = TS_T * TS_ITEMS;     // accesses per scan tile
-constexpr uint32_t TS_AGG_T = 1024;               // threads of the aggregate scan
-constexpr uint32_t TS_RING = 64;                  // undecided-count ring (> the rounds of one host batch)
-constexpr uint32_t TS_ERR_OFF = 1, TS_ERR_KEY = 2, TS_ERR_FULL = 4, TS_ERR_STATE = 8, TS_ERR_TS = 16;
-// counter words (ts_misc); KOR / KNOR are u64 at words 8 and 10; words 12 ..
-// 15 are the engine's
-constexpr uint32_t TS_C_ERR = 0, TS_C_MAXLEN = 1, TS_C_NWR = 2, TS_C_RO = 3, TS_C_COMMIT = 4,
-                   TS_C_HEADS = 5, TS_C_ROWS = 6, TS_C_KOR = 8, TS_C_KNOR = 10, TS_C_ENGINE = 12,
-                   TS_C_RING = 16, TS_C_WORDS = TS_C_RING + TS_RING;
+// error bits next to CHK_ERR_*
+constexpr uint32_t TS_ERR_FULL = 4, TS_ERR_STATE = 8, TS_ERR_TS = 16;
+// counter words next to SEG_C_*; words 12 .. 15 are the engine's
+constexpr uint32_t TS_C_NWR = 2, TS_C_RO = 3, TS_C_COMMIT = 4, TS_C_HEADS = 5, TS_C_ROWS = 6, TS_C_ENGINE = 12,
+                   TS_C_RING = 16, TS_C_WORDS = TS_C_RING + SEG_RING;
+static_assert(TS_TILE == SegWork::TILE && TS_C_WORDS <= SegWork::C_WORDS, "the shared workspace's sizes");
 constexpr uint32_t TS_NONE = ROW_NONE;
 // sorted record word: position | type << 8 | head << 16 | last << 17
 constexpr uint32_t TS_I_HEAD = 1u << 16, TS_I_LAST = 1u << 17;
@@ -56,43 +56,6 @@ __device__ inline uint32_t st_prog(uint32_t w) { return w & 0xFFu; }
 // (tab[s].*WTS); MVCC's wts is the row's latest version.
 using TsProbe = ProbeMix;
 constexpr auto WTS = &RowSlot::a, RTS = &RowSlot::b;
-
-// ---------------------------------------------------------------- check
-// The batch's validity before anything indexes with its offsets and before
-// the row table changes; the key bits that vary (OR of the keys, OR of their
-// complements) for the sort's KeyPack.
-__global__ __launch_bounds__(TS_T) void k_ts_check(const uint32_t* __restrict__ off, uint64_t n,
-                                                   const uint64_t* __restrict__ keys, uint64_t nnz,
-                                                   uint32_t* __restrict__ cnt) {
-  __shared__ uint64_t s_a[TS_T / 64], s_b[TS_T / 64];
-  __shared__ uint32_t s_c[TS_T / 64], s_d[TS_T / 64];
-  uint32_t len = 0, err = 0;
-  uint64_t kor = 0, knor = 0;
-  const uint64_t tid = (uint64_t)blockIdx.x * TS_T + threadIdx.x, stride = (uint64_t)gridDim.x * TS_T;
-  for (uint64_t t = tid; t < n; t += stride) {
-    const uint32_t a0 = off[t], b0 = off[t + 1];
-    if (b0 < a0) err |= TS_ERR_OFF;
-    else len = max(len, b0 - a0);
-    if (t == 0 && a0 != 0) err |= TS_ERR_OFF;
-    if (t == n - 1 && b0 != nnz) err |= TS_ERR_OFF;
-  }
-  for (uint64_t x = tid; x < nnz; x += stride) {
-    const uint64_t k = keys[x];
-    if (k == KEY_EMPTY) err |= TS_ERR_KEY;
-    kor |= k;
-    knor |= ~k;
-  }
-  kor = block_reduce<TS_T / 64, OrOp<uint64_t>>(kor, s_a);
-  knor = block_reduce<TS_T / 64, OrOp<uint64_t>>(knor, s_b);
-  len = block_reduce<TS_T / 64, MaxOp<uint32_t>>(len, s_c);
-  err = block_reduce<TS_T / 64, OrOp<uint32_t>>(err, s_d);
-  if (threadIdx.x == 0) {
-    if (kor) atomicOr((unsigned long long*)&cnt[TS_C_KOR], (unsigned long long)kor);
-    if (knor) atomicOr((unsigned long long*)&cnt[TS_C_KNOR], (unsigned long long)knor);
-    if (len) atomicMax(&cnt[TS_C_MAXLEN], len);
-    if (err) atomicOr(&cnt[TS_C_ERR], err);
-  }
-}
 
 struct TsArgs {
   uint64_t n, m;
@@ -177,7 +140,7 @@ __global__ __launch_bounds__(TS_T) void k_ts_seed(uint64_t m, const uint32_t* __
     if (!(s_info[s] & TS_I_HEAD)) continue;
     bool ins;
     const uint32_t slot = probe_insert<TsProbe>(tab, mask, keys[sv[s]], ins);
-    if (slot == TS_NONE) atomicOr(&cnt[TS_C_ERR], TS_ERR_FULL);
+    if (slot == TS_NONE) atomicOr(&cnt[SEG_C_ERR], TS_ERR_FULL);
     hslot[s] = slot;
     c += ins;
   }
@@ -191,6 +154,7 @@ struct Tq {
   uint64_t de, pe, dw, pw;  // executed: certain / possible; committed writer: certain / possible
   uint32_t f;
 };
+static_assert(sizeof(Tq) == SegWork::AGG_BYTES, "the shared workspace's aggregate size");
 struct TqOp {
   using T = Tq;
   static constexpr bool has_inverse = false;
@@ -215,7 +179,7 @@ struct ScanArgs {
   const uint32_t* stp;
   RowSlot* tab;
   Tq* agg;          // [tiles] the tile aggregates
-  Tq* pre;          // [tiles] their exclusive prefixes (k_ts_aggscan)
+  Tq* pre;          // [tiles] their exclusive prefixes (k_tile_aggscan)
   uint8_t* tdone;   // [tiles] every access of the tile belongs to a decided txn
   ulonglong2* bnd;
   const uint32_t* left;  // txns undecided before this round: 0 = nothing to do
@@ -356,25 +320,6 @@ __global__ __launch_bounds__(TS_T) void k_ts_scan(typename E::Scan A) {
   if constexpr (FINAL && E::MVCC) E::flush(A, out);
 }
 
-// Exclusive scan of the tile aggregates, one workgroup; it also clears the
-// ring word this round's k_ts_advance counts into.
-__global__ __launch_bounds__(TS_AGG_T) void k_ts_aggscan(const Tq* __restrict__ agg, Tq* __restrict__ pre,
-                                                         uint64_t tiles, const uint32_t* left,
-                                                         uint32_t* left_out) {
-  __shared__ Tq s_w[TS_AGG_T / 64];
-  if (left_out && threadIdx.x == 0) *left_out = 0;
-  if (left && *left == 0) return;
-  Tq carry = TqOp::identity();
-  for (uint64_t c0 = 0; c0 < tiles; c0 += TS_AGG_T) {
-    const uint64_t i = c0 + threadIdx.x;
-    const Tq v = i < tiles ? agg[i] : TqOp::identity();
-    Tq total;
-    const Tq ex = block_excl_reuse<TS_AGG_T / 64, TqOp>(v, s_w, total);
-    if (i < tiles) pre[i] = TqOp::combine(carry, ex);
-    carry = TqOp::combine(carry, total);
-  }
-}
-
 // One round of decisions.  P lanes per txn, one access per lane: the first
 // access at or past the progress that does not pass for certain is where the
 // txn aborts (below the certain bound) or stops.  Counts the txns it leaves
@@ -437,13 +382,8 @@ __global__ __launch_bounds__(TS_T) void k_ts_rc(uint64_t n, const uint32_t* __re
     commits += ok;
     bad |= st_state(st) == ST_UNDECIDED;
   }
-  if (bad) atomicOr(&cnt[TS_C_ERR], TS_ERR_STATE);
+  if (bad) atomicOr(&cnt[SEG_C_ERR], TS_ERR_STATE);
   block_add<TS_T / 64>(commits, &cnt[TS_C_COMMIT]);
-}
-
-inline unsigned ts_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
-  const uint64_t b = (items + per_block - 1) / per_block;
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, max_grid));
 }
 
 // ------------------------------------------------------------------ host
@@ -471,7 +411,8 @@ int ts_build(dcc_ctx* ctx, RowTab& rows, const DevBatch& d, const uint64_t* ts_d
              Checks more_checks, BeforeSeed before_seed) {
   const uint64_t n = d.n, m = d.nnz;
   hipStream_t stream = ctx->stream;
-  uint32_t* cnt = (uint32_t*)ctx->ts_misc.p;
+  SegWork& W = ctx->seg;
+  uint32_t* cnt = (uint32_t*)W.misc.p;
   R.n = n;
   R.m = m;
   R.cnt = cnt;
@@ -481,49 +422,41 @@ int ts_build(dcc_ctx* ctx, RowTab& rows, const DevBatch& d, const uint64_t* ts_d
   // reject a malformed batch before anything indexes with its offsets: the row
   // table is untouched by a rejected call
   CK(hipMemsetAsync(cnt, 0, TS_C_WORDS * 4, stream));
-  k_ts_check<<<ts_grid(std::max(n, m), TS_T * 4, R.max_grid), TS_T, 0, stream>>>(d.off, n, d.keys, m, cnt);
+  k_batch_check<true><<<launch_grid(std::max(n, m), CHK_T * 4, R.max_grid), CHK_T, 0, stream>>>(
+      d.off, n, d.keys, m, cnt);
   CK(hipGetLastError());
   CR(more_checks(cnt));
   CK(hipMemcpyAsync(ctx->hmisc, cnt, TS_C_RING * 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
-  uint32_t maxlen = 0;
-  uint64_t varying = 0;
+  BatchShape shape;
   {
     const uint32_t* hc = (const uint32_t*)ctx->hmisc;
-    if (hc[TS_C_ERR] & TS_ERR_OFF) return ctx->fail(DCC_EINVAL, "batch: malformed offsets");
-    if (hc[TS_C_ERR] & TS_ERR_KEY) return ctx->fail(DCC_EINVAL, "batch: key equal to DCC_KEY_RESERVED");
-    if (hc[TS_C_ERR] & TS_ERR_TS) return ctx->fail(DCC_EINVAL, "%s: a timestamp is 0 or UINT64_MAX", E::name);
-    maxlen = hc[TS_C_MAXLEN];
-    if (maxlen > MAX_TXN_LEN)
-      return ctx->fail(DCC_EINVAL, "batch: a txn has %u accesses (> MAX_ROW_PER_TXN=%u)", maxlen, MAX_TXN_LEN);
-    uint64_t kor, knor;
-    memcpy(&kor, hc + TS_C_KOR, 8);
-    memcpy(&knor, hc + TS_C_KNOR, 8);
-    varying = m ? (kor & knor) : 0;  // a bit set in some key and clear in another
+    // a bad timestamp is reported before an over-long txn, as the offsets and the keys are
+    if (!(hc[SEG_C_ERR] & (CHK_ERR_OFF | CHK_ERR_KEY)) && (hc[SEG_C_ERR] & TS_ERR_TS))
+      return ctx->fail(DCC_EINVAL, "%s: a timestamp is 0 or UINT64_MAX", E::name);
+    CR(batch_checked(ctx, hc, m, true, shape));
   }
-  uint32_t lp = 0;
-  while ((1u << lp) < maxlen) lp++;
+  const uint32_t lp = shape.lp;
   R.lp = lp;
   R.per_block = TS_T >> lp;  // txns per workgroup step
-  const KeyPack kp = make_keypack(varying);
+  const KeyPack kp = make_keypack(shape.varying);
   R.tiles = (m + TS_TILE - 1) / TS_TILE;
 
   const bool prof = ctx->profiling;
   CK(hipEventRecord(ctx->ev0, stream));
   if (prof) CK(hipEventRecord(ctx->pev[0], stream));
-  R.A = TsArgs{n, m, d.off, d.keys, d.acctype, ts_dev, lp, (uint4*)ctx->ts_arec.p, (uint32_t*)ctx->ts_stp.p,
+  R.A = TsArgs{n, m, d.off, d.keys, d.acctype, ts_dev, lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p,
                (ulonglong2*)ctx->ts_bnd.p, cnt};
-  uint64_t* kb[2] = {(uint64_t*)ctx->ts_k[0].p, (uint64_t*)ctx->ts_k[1].p};
-  uint32_t* vb[2] = {(uint32_t*)ctx->ts_v[0].p, (uint32_t*)ctx->ts_v[1].p};
-  k_ts_prep<<<ts_grid(n, R.per_block, R.max_grid), TS_T, 0, stream>>>(R.A, kp, kb[0], vb[0]);
+  uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
+  uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
+  k_ts_prep<<<launch_grid(n, R.per_block, R.max_grid), TS_T, 0, stream>>>(R.A, kp, kb[0], vb[0]);
   CK(hipGetLastError());
   R.SA = ScanArgs{};
   if (m) {
     const int cur = radix_sort_u64(kb, vb, m, kp.bits, (uint32_t*)ctx->cv_scratch.p, stream);
     R.sv = vb[cur];
-    k_ts_seg<<<ts_grid(m, TS_T, R.max_grid), TS_T, 0, stream>>>(R.A, kb[cur], vb[cur], (uint32_t*)ctx->ts_stxn.p,
-                                                                (uint32_t*)ctx->ts_sinfo.p,
-                                                                (uint64_t*)ctx->ts_sts.p);
+    k_ts_seg<<<launch_grid(m, TS_T, R.max_grid), TS_T, 0, stream>>>(R.A, kb[cur], vb[cur], (uint32_t*)W.stxn.p,
+                                                                    (uint32_t*)W.sinfo.p, (uint64_t*)W.sts.p);
     CK(hipGetLastError());
     // the table gets room for every row of the epoch before any is entered
     CK(hipMemcpyAsync(ctx->hmisc, cnt, TS_C_RING * 4, hipMemcpyDeviceToHost, stream));
@@ -532,77 +465,51 @@ int ts_build(dcc_ctx* ctx, RowTab& rows, const DevBatch& d, const uint64_t* ts_d
     R.nnz_w = ((const uint32_t*)ctx->hmisc)[TS_C_NWR];
     CR(rows.reserve<TsProbe>(ctx, rows.rows + R.heads));
     CR(before_seed());
-    k_ts_seed<<<ts_grid(m, TS_T, R.max_grid), TS_T, 0, stream>>>(m, (const uint32_t*)ctx->ts_sinfo.p, vb[cur],
-                                                                 d.keys, (RowSlot*)rows.buf.p, rows.mask(),
-                                                                 (uint32_t*)ctx->ts_hslot.p, cnt);
+    k_ts_seed<<<launch_grid(m, TS_T, R.max_grid), TS_T, 0, stream>>>(m, (const uint32_t*)W.sinfo.p, vb[cur], d.keys,
+                                                                     (RowSlot*)rows.buf.p, rows.mask(),
+                                                                     (uint32_t*)ctx->ts_hslot.p, cnt);
     CK(hipGetLastError());
-    CK(hipMemsetAsync(ctx->ts_tdone.p, 0, R.tiles, stream));
+    CK(hipMemsetAsync(W.tdone.p, 0, R.tiles, stream));
     R.SA = ScanArgs{m,
-                    (const uint32_t*)ctx->ts_stxn.p,
-                    (const uint32_t*)ctx->ts_sinfo.p,
-                    (const uint64_t*)ctx->ts_sts.p,
+                    (const uint32_t*)W.stxn.p,
+                    (const uint32_t*)W.sinfo.p,
+                    (const uint64_t*)W.sts.p,
                     vb[cur],
                     (const uint32_t*)ctx->ts_hslot.p,
                     R.A.stp,
                     (RowSlot*)rows.buf.p,
-                    (Tq*)ctx->ts_agg.p,
-                    (Tq*)ctx->ts_agg.p + R.tiles,
-                    (uint8_t*)ctx->ts_tdone.p,
+                    (Tq*)W.agg.p,
+                    (Tq*)W.agg.p + R.tiles,
+                    (uint8_t*)W.tdone.p,
                     R.A.bnd,
                     nullptr,
-                    &cnt[TS_C_ERR]};
+                    &cnt[SEG_C_ERR]};
   }
   if (prof) CK(hipEventRecord(ctx->pev[1], stream));
   return DCC_OK;
 }
 
-// The rounds: round r reads the undecided count of round r - 1 from ring[r %
-// TS_RING] (nothing to do at 0) and counts into ring[(r + 1) % TS_RING], which
-// its k_ts_aggscan cleared.  Several rounds are enqueued between host
-// synchronisations; rounds past the fixed point return at once.  pev[2] is
-// recorded behind round 1, pev[3] at the end.  `scan(SA)`: the engine's
-// k_ts_scan argument for these launches.
+// The rounds (seg_rounds.h's loop): a round is reduce / scan of the tile
+// aggregates, which clears the ring word the round counts into / apply /
+// advance.  The lowest undecided txn is decided in every round: at most n of
+// them.  `scan(SA)`: the engine's k_ts_scan argument for these launches.
 template <class E, class MakeScan>
 int ts_rounds(dcc_ctx* ctx, TsRun& R, MakeScan scan) {
   hipStream_t stream = ctx->stream;
-  const bool prof = ctx->profiling;
-  const uint64_t n = R.n, m = R.m, tiles = R.tiles;
-  uint32_t r = 1, rounds = 0;
-  uint32_t batch = std::min<uint32_t>(2, ctx->batch_max);
-  bool done = false;
-  const unsigned agrid = ts_grid(n, R.per_block, R.max_grid);
-  while (!done) {
-    const uint32_t r0 = r;
-    for (uint32_t q = 0; q < batch; q++, r++) {
-      const uint32_t* left = &R.ring[r % TS_RING];
-      uint32_t* left_out = &R.ring[(r + 1) % TS_RING];
-      if (m) {
-        R.SA.left = left;
-        k_ts_scan<false, false, E><<<(unsigned)tiles, TS_T, 0, stream>>>(scan(R.SA));
-        k_ts_aggscan<<<1, TS_AGG_T, 0, stream>>>(R.SA.agg, R.SA.pre, tiles, left, left_out);
-        k_ts_scan<true, false, E><<<(unsigned)tiles, TS_T, 0, stream>>>(scan(R.SA));
-      } else {
-        k_ts_aggscan<<<1, TS_AGG_T, 0, stream>>>(nullptr, nullptr, 0, left, left_out);
-      }
-      k_ts_advance<<<agrid, TS_T, 0, stream>>>(R.A, left, left_out);
-      if (prof && r == 1) CK(hipEventRecord(ctx->pev[2], stream));
-    }
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(ctx->hmisc, R.ring, TS_RING * 4, hipMemcpyDeviceToHost, stream));
-    CK(hipStreamSynchronize(stream));
-    const uint32_t* hr = (const uint32_t*)ctx->hmisc;
-    for (uint32_t q = r0; q < r; q++)
-      if (hr[(q + 1) % TS_RING] == 0) {
-        rounds = q;
-        done = true;
-        break;
-      }
-    if (!done && r > n + 2) return ctx->fail(DCC_EIO, "%s: fixed point did not converge", E::name);
-    batch = std::min<uint32_t>(batch * 2, std::min<uint32_t>(ctx->batch_max, TS_RING / 2));
-  }
-  R.rounds = rounds;
-  if (prof) CK(hipEventRecord(ctx->pev[3], stream));
-  return DCC_OK;
+  const uint64_t m = R.m, tiles = R.tiles;
+  const unsigned agrid = launch_grid(R.n, R.per_block, R.max_grid);
+  return rounds_loop(ctx, R.ring, R.n, R.n + 2, E::name, R.rounds,
+                     [&](uint32_t, const uint32_t* left, uint32_t* left_out, uint64_t) {
+                       if (m) {
+                         R.SA.left = left;
+                         k_ts_scan<false, false, E><<<(unsigned)tiles, TS_T, 0, stream>>>(scan(R.SA));
+                         k_tile_aggscan<TqOp><<<1, SEG_AGG_T, 0, stream>>>(R.SA.agg, R.SA.pre, tiles, left, left_out);
+                         k_ts_scan<true, false, E><<<(unsigned)tiles, TS_T, 0, stream>>>(scan(R.SA));
+                       } else {
+                         k_tile_aggscan<TqOp><<<1, SEG_AGG_T, 0, stream>>>(nullptr, nullptr, 0, left, left_out);
+                       }
+                       k_ts_advance<<<agrid, TS_T, 0, stream>>>(R.A, left, left_out);
+                     });
 }
 
 }  // namespace

@@ -57,11 +57,12 @@
 //           k_wd_seg      sorted records, row heads, own-run heads
 //           k_wd_scan     per 1,024-access tile: its aggregate, or behind the
 //                         scanned aggregates four bits per dynamic access
-//           k_wd_aggscan  exclusive scan of the tile aggregates (one workgroup)
 //           k_wd_advance  one round of decisions
 //           k_wd_final    rc, pos, conflict ordinals, counts
 //           k_wd_rprep / k_wd_rkey / k_wd_rseg / k_wd_rscan / k_wd_rgone: the release
-// No workgroup waits on another.
+// No workgroup waits on another.  The offsets' and keys' rules of the check,
+// k_tile_aggscan, the rounds loop and the workspaces are seg_rounds.h's
+// (DESIGN.md §8n).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -74,6 +75,7 @@
 #include "nowait_lanes.h"
 #include "occ_kernels.h"
 #include "radix_sort.h"
+#include "seg_rounds.h"
 
 using namespace dcc;
 
@@ -82,13 +84,17 @@ namespace {
 constexpr uint32_t WD_T = 256;      // threads per workgroup
 constexpr uint32_t WD_ITEMS = 4;    // consecutive sorted accesses per thread
 constexpr uint32_t WD_TILE = WD_T * WD_ITEMS;  // accesses per scan tile
-constexpr uint32_t WD_AGG_T = 1024;            // threads of the aggregate scan
-constexpr uint32_t WD_RING = 64;               // undecided-count ring (> the rounds of one host batch)
-constexpr uint32_t WD_ERR_OFF = 1, WD_ERR_KEY = 2, WD_ERR_RC = 4, WD_ERR_POS = 8, WD_ERR_STATE = 16;
-// counter words; KOR / KNOR / TOR / TNOR are u64 at words 8, 10, 12, 14
-constexpr uint32_t WD_C_ERR = 0, WD_C_MAXLEN = 1, WD_C_NEX = 2, WD_C_RO = 3, WD_C_OK = 4, WD_C_DIE = 5,
-                   WD_C_WAIT = 6, WD_C_LEFT = 7, WD_C_KOR = 8, WD_C_KNOR = 10, WD_C_TOR = 12, WD_C_TNOR = 14,
-                   WD_C_PROM = 16, WD_C_RING = 20, WD_C_WORDS = WD_C_RING + WD_RING;
+// the rounds loop's ring, SEG_RING of seg_rounds.h, restated as a number here,
+// where the tests that size their chains past it read the geometry
+constexpr uint32_t WD_RING = 64;
+static_assert(WD_RING == SEG_RING, "the ring is seg_rounds.h's");
+// error bits next to CHK_ERR_*
+constexpr uint32_t WD_ERR_RC = 4, WD_ERR_POS = 8, WD_ERR_STATE = 16;
+// counter words next to SEG_C_*; TOR / TNOR are u64 at words 12, 14
+constexpr uint32_t WD_C_NEX = 2, WD_C_RO = 3, WD_C_OK = 4, WD_C_DIE = 5, WD_C_WAIT = 6, WD_C_LEFT = 7,
+                   WD_C_TOR = 12, WD_C_TNOR = 14, WD_C_PROM = 16, WD_C_RING = 20,
+                   WD_C_WORDS = WD_C_RING + SEG_RING;
+static_assert(WD_TILE == SegWork::TILE && WD_C_WORDS <= SegWork::C_WORDS, "the shared workspace's sizes");
 // txn word: state << 16 | cap << 8 | progress.  cap: the first access at or
 // past the progress of an undecided txn with a certain conflict (WS_NOCAP: none
 // known): it owns nothing from there on and waits there at the latest
@@ -127,15 +133,8 @@ __global__ __launch_bounds__(WD_T) void k_wd_check(const uint32_t* __restrict__ 
   uint64_t kor = 0, knor = 0, tor = 0, tnor = 0;
   const uint64_t tid = (uint64_t)blockIdx.x * WD_T + threadIdx.x, stride = (uint64_t)gridDim.x * WD_T;
   for (uint64_t t = tid; t < n; t += stride) {
-    const uint32_t a0 = off[t], b0 = off[t + 1];
-    if (t == 0 && a0 != 0) err |= WD_ERR_OFF;
-    if (t == n - 1 && b0 != nnz) err |= WD_ERR_OFF;
-    if (b0 < a0) {
-      err |= WD_ERR_OFF;
-      continue;
-    }
-    const uint32_t l = b0 - a0;
-    len = max(len, l);
+    uint32_t l;
+    if (!check_span(off, t, n, nnz, err, len, l)) continue;
     const uint8_t r = rc[t];
     const uint32_t p = pos[t];
     if (!wd_state_ok(r)) err |= WD_ERR_RC;
@@ -146,12 +145,7 @@ __global__ __launch_bounds__(WD_T) void k_wd_check(const uint32_t* __restrict__ 
     tnor |= ~v;
     count += leave ? (leave[t] != 0 && r != DCC_WD_GONE) : (r == DCC_WD_RUN);
   }
-  for (uint64_t x = tid; x < nnz; x += stride) {
-    const uint64_t k = keys[x];
-    if (k == KEY_EMPTY) err |= WD_ERR_KEY;
-    kor |= k;
-    knor |= ~k;
-  }
+  for (uint64_t x = tid; x < nnz; x += stride) check_key(keys[x], err, kor, knor);
   kor = block_reduce<WD_T / 64, OrOp<uint64_t>>(kor, s_a);
   knor = block_reduce<WD_T / 64, OrOp<uint64_t>>(knor, s_b);
   tor = block_reduce<WD_T / 64, OrOp<uint64_t>>(tor, s_e);
@@ -159,12 +153,12 @@ __global__ __launch_bounds__(WD_T) void k_wd_check(const uint32_t* __restrict__ 
   len = block_reduce<WD_T / 64, MaxOp<uint32_t>>(len, s_c);
   err = block_reduce<WD_T / 64, OrOp<uint32_t>>(err, s_d);
   if (threadIdx.x == 0) {
-    if (kor) atomicOr((unsigned long long*)&cnt[WD_C_KOR], (unsigned long long)kor);
-    if (knor) atomicOr((unsigned long long*)&cnt[WD_C_KNOR], (unsigned long long)knor);
+    if (kor) atomicOr((unsigned long long*)&cnt[SEG_C_KOR], (unsigned long long)kor);
+    if (knor) atomicOr((unsigned long long*)&cnt[SEG_C_KNOR], (unsigned long long)knor);
     if (tor) atomicOr((unsigned long long*)&cnt[WD_C_TOR], (unsigned long long)tor);
     if (tnor) atomicOr((unsigned long long*)&cnt[WD_C_TNOR], (unsigned long long)tnor);
-    if (len) atomicMax(&cnt[WD_C_MAXLEN], len);
-    if (err) atomicOr(&cnt[WD_C_ERR], err);
+    if (len) atomicMax(&cnt[SEG_C_MAXLEN], len);
+    if (err) atomicOr(&cnt[SEG_C_ERR], err);
   }
   block_add<WD_T / 64>(count, leave ? &cnt[WD_C_LEFT] : &cnt[WD_C_RING + 1]);
 }
@@ -269,6 +263,7 @@ struct Wq {
   uint64_t cmin, pmin, cw, pw;
   uint32_t bits;
 };
+static_assert(sizeof(Wq) == SegWork::AGG_BYTES, "the shared workspace's aggregate size");
 struct WqOp {
   using T = Wq;
   static constexpr bool has_inverse = false;
@@ -293,7 +288,7 @@ struct WdScan {
   const uint32_t* sv;
   const uint32_t* stp;
   Wq* agg;          // [tiles] the tile aggregates
-  Wq* pre;          // [tiles] their exclusive prefixes (k_wd_aggscan)
+  Wq* pre;          // [tiles] their exclusive prefixes (k_tile_aggscan)
   uint8_t* tdone;   // [tiles] no access of the tile belongs to an undecided txn
   uint8_t* flg;
   const uint32_t* left;  // txns undecided before this round: 0 = nothing to do
@@ -377,27 +372,6 @@ __global__ __launch_bounds__(WD_T) void k_wd_scan(WdScan A) {
   }
 }
 
-// Exclusive scan of the tile aggregates, one workgroup; it also clears the
-// ring word this round's k_wd_advance counts into.
-template <class Op>
-__global__ __launch_bounds__(WD_AGG_T) void k_wd_aggscan(const typename Op::T* __restrict__ agg,
-                                                         typename Op::T* __restrict__ pre, uint64_t tiles,
-                                                         const uint32_t* left, uint32_t* left_out) {
-  using T = typename Op::T;
-  __shared__ T s_w[WD_AGG_T / 64];
-  if (left_out && threadIdx.x == 0) *left_out = 0;
-  if (left && *left == 0) return;
-  T carry = Op::identity();
-  for (uint64_t c0 = 0; c0 < tiles; c0 += WD_AGG_T) {
-    const uint64_t i = c0 + threadIdx.x;
-    const T v = i < tiles ? agg[i] : Op::identity();
-    T total;
-    const T ex = block_excl_reuse<WD_AGG_T / 64, Op>(v, s_w, total);
-    if (i < tiles) pre[i] = Op::combine(carry, ex);
-    carry = Op::combine(carry, total);
-  }
-}
-
 // One round of decisions.  P lanes per txn, one access per lane: the first
 // access at or past the progress with a possible conflict is where the txn
 // dies, waits or stops.  Counts the txns it leaves undecided.
@@ -468,7 +442,7 @@ __global__ __launch_bounds__(WD_T) void k_wd_final(uint64_t n, const uint32_t* _
     }
     if (conflict) conflict[t] = c;
   }
-  if (bad) atomicOr(&cnt[WD_C_ERR], WD_ERR_STATE);
+  if (bad) atomicOr(&cnt[SEG_C_ERR], WD_ERR_STATE);
   block_add<WD_T / 64>(ok, &cnt[WD_C_OK]);
   __syncthreads();
   block_add<WD_T / 64>(die, &cnt[WD_C_DIE]);
@@ -603,31 +577,19 @@ __global__ __launch_bounds__(WD_T) void k_wd_rgone(uint64_t n, const uint8_t* __
     if (leave[t]) rc[t] = DCC_WD_GONE;
 }
 
-inline unsigned wd_grid(uint64_t items, uint64_t per_block, unsigned max_grid) {
-  const uint64_t b = (items + per_block - 1) / per_block;
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, max_grid));
-}
-
-// What the check left in the pinned mirror: the rejection, or the longest txn
-// and the varying bits.
-struct WdChecked {
-  uint32_t maxlen = 0, count = 0;
-  uint64_t kvar = 0, tvar = 0;
+// What the check left in the pinned mirror: the rejection, or the batch's
+// shape, the timestamp bits that vary and the RUN txns / leavers.
+struct WdChecked : BatchShape {
+  uint32_t count = 0;
+  uint64_t tvar = 0;
 };
 int wd_checked(dcc_ctx* ctx, const uint32_t* hc, uint64_t n, uint64_t m, bool release, WdChecked& c) {
-  const uint32_t err = hc[WD_C_ERR];
-  if (err & WD_ERR_OFF) return ctx->fail(DCC_EINVAL, "batch: malformed offsets");
-  if (err & WD_ERR_KEY) return ctx->fail(DCC_EINVAL, "batch: key equal to DCC_KEY_RESERVED");
-  c.maxlen = hc[WD_C_MAXLEN];
-  if (c.maxlen > MAX_TXN_LEN)
-    return ctx->fail(DCC_EINVAL, "batch: a txn has %u accesses (> MAX_ROW_PER_TXN=%u)", c.maxlen, MAX_TXN_LEN);
+  const uint32_t err = hc[SEG_C_ERR];
+  CR(batch_checked(ctx, hc, m, true, c));
   if (err & WD_ERR_RC) return ctx->fail(DCC_EINVAL, "waitdie: an rc byte is none of the five states");
   if (err & WD_ERR_POS)
     return ctx->fail(DCC_EINVAL, "waitdie: a pos does not fit its state (pos > len, RCOK below len, WAIT at len)");
   uint64_t a, b;
-  memcpy(&a, hc + WD_C_KOR, 8);
-  memcpy(&b, hc + WD_C_KNOR, 8);
-  c.kvar = m ? (a & b) : 0;  // a bit set in some key and clear in another
   memcpy(&a, hc + WD_C_TOR, 8);
   memcpy(&b, hc + WD_C_TNOR, 8);
   c.tvar = n ? (a & b) : 0;
@@ -639,20 +601,8 @@ int wd_checked(dcc_ctx* ctx, const uint32_t* hc, uint64_t n, uint64_t m, bool re
 
 int dcc_ctx::waitdie_reserve(uint64_t n, uint64_t nnz, bool host_arrays) {
   const uint64_t nn = std::max<uint64_t>(n, 1), mm = std::max<uint64_t>(nnz, 1);
-  const uint64_t tiles = (mm + WD_TILE - 1) / WD_TILE;
-  CR(wd_misc.ensure(this, WD_C_WORDS * 4, "waitdie counters"));
-  CR(wd_stp.ensure(this, nn * 4, "waitdie txn words"));
-  CR(wd_arec.ensure(this, mm * 16, "waitdie access records"));
-  for (int q = 0; q < 2; q++) {
-    CR(wd_k[q].ensure(this, mm * 8, "waitdie sort keys"));
-    CR(wd_v[q].ensure(this, mm * 4, "waitdie sort values"));
-  }
-  CR(wd_stxn.ensure(this, mm * 4, "waitdie sorted txns"));
-  CR(wd_sinfo.ensure(this, mm * 4, "waitdie sorted records"));
-  CR(wd_sts.ensure(this, mm * 8, "waitdie sorted timestamps"));
+  CR(seg.reserve(this, n, nnz));
   CR(wd_flg.ensure(this, mm, "waitdie access flags"));
-  CR(wd_agg.ensure(this, 2 * tiles * sizeof(Wq), "waitdie tile aggregates and prefixes"));
-  CR(wd_tdone.ensure(this, tiles, "waitdie tile flags"));
   CR(cv_scratch.ensure(this, rs_scratch_words(mm) * 4 + 64, "radix scratch"));
   if (host_arrays) {
     CR(wd_hts.ensure(this, nn * 8, "waitdie timestamps"));
@@ -710,7 +660,8 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   const uint8_t* none;
   CR(waitdie_stage(n, dev, ts_in, rc_io, pos_io, nullptr, ts_dev, rc_dev, pos_dev, none));
   uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)wd_conf.p) : nullptr;
-  uint32_t* cnt = (uint32_t*)wd_misc.p;
+  SegWork& W = seg;
+  uint32_t* cnt = (uint32_t*)W.misc.p;
   uint32_t* ring = cnt + WD_C_RING;
   const unsigned max_grid = (unsigned)n_cu * 16;
   const bool prof = profiling;
@@ -718,90 +669,67 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   // reject a malformed batch or state before anything indexes with it: rc,
   // pos and the outputs are untouched by a rejected call
   CK(hipMemsetAsync(cnt, 0, WD_C_WORDS * 4, stream));
-  k_wd_check<<<wd_grid(std::max(n, m), WD_T * 4, max_grid), WD_T, 0, stream>>>(d.off, n, d.keys, m, ts_dev, rc_dev,
-                                                                            pos_dev, nullptr, cnt);
+  k_wd_check<<<launch_grid(std::max(n, m), WD_T * 4, max_grid), WD_T, 0, stream>>>(
+      d.off, n, d.keys, m, ts_dev, rc_dev, pos_dev, nullptr, cnt);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(hmisc, cnt, WD_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   WdChecked c;
   CR(wd_checked(this, (const uint32_t*)hmisc, n, m, false, c));
-  const KeyPack kp = make_keypack(c.kvar);
+  const KeyPack kp = make_keypack(c.varying);
   if (kp.bits > 63) return fail(DCC_ENOTSUP, "waitdie: the keys vary in all 64 bits");
-  uint32_t lp = 0;
-  while ((1u << lp) < c.maxlen) lp++;
+  const uint32_t lp = c.lp;
   const uint64_t per_block = WD_T >> lp, tiles = (m + WD_TILE - 1) / WD_TILE;
 
   CK(hipEventRecord(ev0, stream));
   if (prof) CK(hipEventRecord(pev[0], stream));
   const WdArgs A{n,  m,  d.off, d.keys, d.acctype, ts_dev, rc_dev, pos_dev,
-                 lp, (uint4*)wd_arec.p, (uint32_t*)wd_stp.p, (uint8_t*)wd_flg.p, cnt};
-  uint64_t* kb[2] = {(uint64_t*)wd_k[0].p, (uint64_t*)wd_k[1].p};
-  uint32_t* vb[2] = {(uint32_t*)wd_v[0].p, (uint32_t*)wd_v[1].p};
-  const unsigned agrid = wd_grid(n, per_block, max_grid);
+                 lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p, (uint8_t*)wd_flg.p, cnt};
+  uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
+  uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
+  const unsigned agrid = launch_grid(n, per_block, max_grid);
   k_wd_prep<<<agrid, WD_T, 0, stream>>>(A, kp, kb[0], vb[0]);
   CK(hipGetLastError());
   WdScan SA{};
   if (m) {
     const int cur = radix_sort_u64(kb, vb, m, kp.bits + 1, (uint32_t*)cv_scratch.p, stream);
-    k_wd_seg<<<wd_grid(m, WD_T, max_grid), WD_T, 0, stream>>>(m, A.arec, kb[cur], vb[cur], (uint32_t*)wd_stxn.p,
-                                                             (uint32_t*)wd_sinfo.p, (uint64_t*)wd_sts.p);
+    k_wd_seg<<<launch_grid(m, WD_T, max_grid), WD_T, 0, stream>>>(m, A.arec, kb[cur], vb[cur], (uint32_t*)W.stxn.p,
+                                                                  (uint32_t*)W.sinfo.p, (uint64_t*)W.sts.p);
     CK(hipGetLastError());
-    CK(hipMemsetAsync(wd_tdone.p, 0, tiles, stream));
-    SA = WdScan{m,      (const uint32_t*)wd_stxn.p, (const uint32_t*)wd_sinfo.p, (const uint64_t*)wd_sts.p,
-                vb[cur], A.stp,                     (Wq*)wd_agg.p,               (Wq*)wd_agg.p + tiles,
-                (uint8_t*)wd_tdone.p, A.flg,        nullptr};
+    CK(hipMemsetAsync(W.tdone.p, 0, tiles, stream));
+    SA = WdScan{m,      (const uint32_t*)W.stxn.p, (const uint32_t*)W.sinfo.p, (const uint64_t*)W.sts.p,
+                vb[cur], A.stp,                     (Wq*)W.agg.p,               (Wq*)W.agg.p + tiles,
+                (uint8_t*)W.tdone.p, A.flg,        nullptr};
   }
   if (prof) CK(hipEventRecord(pev[1], stream));
 
-  // The rounds: round r reads the undecided count of round r - 1 from ring[r %
-  // WD_RING] (nothing to do at 0) and counts into ring[(r + 1) % WD_RING],
-  // which its k_wd_aggscan cleared.  Several rounds are enqueued between host
-  // synchronisations; rounds past the fixed point return at once.
-  uint32_t r = 1, rounds = 0;
-  uint32_t batch = std::min<uint32_t>(2, batch_max);
-  bool done = false;
-  while (!done) {
-    const uint32_t r0 = r;
-    for (uint32_t q = 0; q < batch; q++, r++) {
-      const uint32_t* left = &ring[r % WD_RING];
-      uint32_t* left_out = &ring[(r + 1) % WD_RING];
-      if (m) {
-        SA.left = left;
-        k_wd_scan<false><<<(unsigned)tiles, WD_T, 0, stream>>>(SA);
-        k_wd_aggscan<WqOp><<<1, WD_AGG_T, 0, stream>>>(SA.agg, SA.pre, tiles, left, left_out);
-        k_wd_scan<true><<<(unsigned)tiles, WD_T, 0, stream>>>(SA);
-      } else {
-        k_wd_aggscan<WqOp><<<1, WD_AGG_T, 0, stream>>>(nullptr, nullptr, 0, left, left_out);
-      }
-      k_wd_advance<<<agrid, WD_T, 0, stream>>>(A, left, left_out);
-      if (prof && r == 1) CK(hipEventRecord(pev[2], stream));
-    }
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(hmisc, ring, WD_RING * 4, hipMemcpyDeviceToHost, stream));
-    CK(hipStreamSynchronize(stream));
-    const uint32_t* hr = (const uint32_t*)hmisc;
-    for (uint32_t q = r0; q < r; q++)
-      if (hr[(q + 1) % WD_RING] == 0) {
-        rounds = q;
-        done = true;
-        break;
-      }
-    // the lowest undecided txn is decided or moves its progress in every round
-    if (!done && r > n + m + 2) return fail(DCC_EIO, "waitdie: fixed point did not converge");
-    batch = std::min<uint32_t>(batch * 2, std::min<uint32_t>(batch_max, WD_RING / 2));
-  }
-  if (prof) CK(hipEventRecord(pev[3], stream));
+  // The rounds (seg_rounds.h's loop): reduce / scan of the tile aggregates,
+  // which clears the ring word the round counts into / apply / advance.  The
+  // lowest undecided txn is decided or moves its progress in every round.
+  uint32_t rounds = 0;
+  CR(rounds_loop(this, ring, n, n + m + 2, "waitdie", rounds,
+                 [&](uint32_t, const uint32_t* left, uint32_t* left_out, uint64_t) {
+                   if (m) {
+                     SA.left = left;
+                     k_wd_scan<false><<<(unsigned)tiles, WD_T, 0, stream>>>(SA);
+                     k_tile_aggscan<WqOp><<<1, SEG_AGG_T, 0, stream>>>(SA.agg, SA.pre, tiles, left, left_out);
+                     k_wd_scan<true><<<(unsigned)tiles, WD_T, 0, stream>>>(SA);
+                   } else {
+                     k_tile_aggscan<WqOp><<<1, SEG_AGG_T, 0, stream>>>(nullptr, nullptr, 0, left, left_out);
+                   }
+                   k_wd_advance<<<agrid, WD_T, 0, stream>>>(A, left, left_out);
+                 }));
 
   // rc / pos of a host call stay as they were unless the decisions are sound:
   // the final pass writes the staged copies
-  k_wd_final<<<wd_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, A.stp, rc_dev, pos_dev, conf_dev, cnt);
+  k_wd_final<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, A.stp, rc_dev, pos_dev, conf_dev, cnt);
   CK(hipGetLastError());
   if (prof) CK(hipEventRecord(pev[4], stream));
   CK(hipEventRecord(ev1, stream));
   CK(hipMemcpyAsync(hmisc, cnt, WD_C_RING * 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
-  if (hc[WD_C_ERR] & WD_ERR_STATE) return fail(DCC_EIO, "waitdie: inconsistent decisions");
+  if (hc[SEG_C_ERR] & WD_ERR_STATE) return fail(DCC_EIO, "waitdie: inconsistent decisions");
   S.rounds = rounds;
   S.n_commit = hc[WD_C_OK];
   S.n_abort = hc[WD_C_DIE];
@@ -846,34 +774,34 @@ int dcc_ctx::waitdie_release(const dcc_batch* b, const uint64_t* ts_in, uint8_t*
   uint32_t* pos_dev;
   const uint8_t* leave_dev;
   CR(waitdie_stage(n, dev, ts_in, rc_io, pos_io, leave_in, ts_dev, rc_dev, pos_dev, leave_dev));
-  uint32_t* cnt = (uint32_t*)wd_misc.p;
+  SegWork& W = seg;
+  uint32_t* cnt = (uint32_t*)W.misc.p;
   const unsigned max_grid = (unsigned)n_cu * 16;
 
   CK(hipMemsetAsync(cnt, 0, WD_C_WORDS * 4, stream));
-  k_wd_check<<<wd_grid(std::max(n, m), WD_T * 4, max_grid), WD_T, 0, stream>>>(d.off, n, d.keys, m, ts_dev, rc_dev,
-                                                                            pos_dev, leave_dev, cnt);
+  k_wd_check<<<launch_grid(std::max(n, m), WD_T * 4, max_grid), WD_T, 0, stream>>>(
+      d.off, n, d.keys, m, ts_dev, rc_dev, pos_dev, leave_dev, cnt);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(hmisc, cnt, WD_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   WdChecked c;
   CR(wd_checked(this, (const uint32_t*)hmisc, n, m, true, c));
-  const KeyPack kp = make_keypack(c.kvar), tp = make_keypack(c.tvar);
+  const KeyPack kp = make_keypack(c.varying), tp = make_keypack(c.tvar);
   if (kp.bits > 63) return fail(DCC_ENOTSUP, "waitdie: the keys vary in all 64 bits");
-  uint32_t lp = 0;
-  while ((1u << lp) < c.maxlen) lp++;
+  const uint32_t lp = c.lp;
   const uint64_t per_block = WD_T >> lp, tiles = (m + WD_TILE - 1) / WD_TILE;
 
   CK(hipEventRecord(ev0, stream));
   const WdArgs A{n,  m,  d.off, d.keys, d.acctype, ts_dev, rc_dev, pos_dev,
-                 lp, (uint4*)wd_arec.p, (uint32_t*)wd_stp.p, (uint8_t*)wd_flg.p, cnt};
+                 lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p, (uint8_t*)wd_flg.p, cnt};
   if (m) {
-    uint64_t* kb[2] = {(uint64_t*)wd_k[0].p, (uint64_t*)wd_k[1].p};
-    uint32_t* vb[2] = {(uint32_t*)wd_v[0].p, (uint32_t*)wd_v[1].p};
-    const unsigned mgrid = wd_grid(m, WD_T, max_grid);
+    uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
+    uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
+    const unsigned mgrid = launch_grid(m, WD_T, max_grid);
     // the records hold what the passes below need of rc / pos / leave: the
     // state is only written behind them (the checked offsets cover every
     // access, so k_wd_rprep writes every key and record)
-    k_wd_rprep<<<wd_grid(n, per_block, max_grid), WD_T, 0, stream>>>(A, leave_dev, tp, kb[0], vb[0]);
+    k_wd_rprep<<<launch_grid(n, per_block, max_grid), WD_T, 0, stream>>>(A, leave_dev, tp, kb[0], vb[0]);
     CK(hipGetLastError());
     const int c1 = radix_sort_u64(kb, vb, m, tp.bits, (uint32_t*)cv_scratch.p, stream);
     uint64_t* kb2[2] = {kb[c1], kb[c1 ^ 1]};
@@ -881,17 +809,17 @@ int dcc_ctx::waitdie_release(const dcc_batch* b, const uint64_t* ts_in, uint8_t*
     k_wd_rkey<<<mgrid, WD_T, 0, stream>>>(m, A.arec, d.keys, kp, vb2[0], kb2[0]);
     CK(hipGetLastError());
     const int c2 = radix_sort_u64(kb2, vb2, m, kp.bits + 1, (uint32_t*)cv_scratch.p, stream);
-    k_wd_rseg<<<mgrid, WD_T, 0, stream>>>(m, A.arec, kb2[c2], vb2[c2], (uint32_t*)wd_stxn.p,
-                                          (uint32_t*)wd_sinfo.p);
+    k_wd_rseg<<<mgrid, WD_T, 0, stream>>>(m, A.arec, kb2[c2], vb2[c2], (uint32_t*)W.stxn.p,
+                                          (uint32_t*)W.sinfo.p);
     CK(hipGetLastError());
-    const WdRel R{m,       (const uint32_t*)wd_stxn.p, (const uint32_t*)wd_sinfo.p, (uint64_t*)wd_agg.p,
-                  (uint64_t*)wd_agg.p + tiles, rc_dev, pos_dev,                     cnt};
+    const WdRel R{m,       (const uint32_t*)W.stxn.p, (const uint32_t*)W.sinfo.p, (uint64_t*)W.agg.p,
+                  (uint64_t*)W.agg.p + tiles, rc_dev, pos_dev,                     cnt};
     k_wd_rscan<false><<<(unsigned)tiles, WD_T, 0, stream>>>(R);
-    k_wd_aggscan<RqOp><<<1, WD_AGG_T, 0, stream>>>(R.agg, R.pre, tiles, nullptr, nullptr);
+    k_tile_aggscan<RqOp><<<1, SEG_AGG_T, 0, stream>>>(R.agg, R.pre, tiles, nullptr, nullptr);
     k_wd_rscan<true><<<(unsigned)tiles, WD_T, 0, stream>>>(R);
     CK(hipGetLastError());
   }
-  k_wd_rgone<<<wd_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, leave_dev, rc_dev);
+  k_wd_rgone<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, leave_dev, rc_dev);
   CK(hipGetLastError());
   CK(hipEventRecord(ev1, stream));
   CK(hipMemcpyAsync(hmisc, cnt, WD_C_RING * 4, hipMemcpyDeviceToHost, stream));
