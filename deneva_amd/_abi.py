@@ -105,6 +105,25 @@ class SelectOut(C.Structure):
     ]
 
 
+class WaitdieCarryArgs(C.Structure):
+    """dcc_waitdie_carry_args: the population, the fresh arrivals and where both go."""
+    _fields_ = [
+        ("batch", C.POINTER(Batch)),
+        ("ts", C.c_void_p),
+        ("rc", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("revive", C.c_void_p),
+        ("src_in", C.c_void_p),
+        ("fresh", C.POINTER(Batch)),
+        ("fresh_ts", C.c_void_p),
+        ("fresh_src_base", C.c_uint32),
+        ("out", C.POINTER(SelectOut)),
+        ("out_ts", C.c_void_p),
+        ("out_rc", C.c_void_p),
+        ("out_pos", C.c_void_p),
+    ]
+
+
 class AbortqParams(C.Structure):
     """dcc_abortq_params: room, penalty and policy of an abort queue."""
     _fields_ = [
@@ -290,6 +309,11 @@ _SIGS = [
     ("dcc_waitdie_release", C.c_int,
      [_P, C.POINTER(Batch), _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     ("dcc_waitdie_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
+    ("dcc_waitdie_carry", C.c_int,
+     [_P, C.POINTER(WaitdieCarryArgs), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+      C.POINTER(Stats)]),
+    ("dcc_waitdie_carry_alg_bytes", C.c_uint64,
+     [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int]),
     ("dcc_batch_select", C.c_int,
      [_P, C.POINTER(Batch), _P, C.c_uint8, _P, C.POINTER(SelectOut), C.POINTER(C.c_uint64),
       C.POINTER(C.c_uint64), C.POINTER(Stats)]),

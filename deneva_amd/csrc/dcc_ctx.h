@@ -552,6 +552,14 @@ struct dcc_ctx {
                     dcc_stats* st);
   int waitdie_release(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
                       uint64_t* out_left, uint64_t* out_promoted, dcc_stats* st);
+  // the population's carry between two epochs (waitdie_carry.hip).  Control
+  // words and tile pairs are the select's; of a host call the population's
+  // state goes through the staging above (revive through wd_hleave, src_in
+  // through sel_src), the fresh batch and the outputs through these
+  DevBuf wc_foff, wc_fkeys, wc_fat, wc_fts, wc_out;
+  int carry_reserve(uint64_t n, uint64_t nnz);
+  int waitdie_carry(const dcc_waitdie_carry_args* a, uint64_t* out_n, uint64_t* out_nnz, uint64_t* out_kept,
+                    dcc_stats* st);
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes

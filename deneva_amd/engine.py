@@ -626,6 +626,94 @@ class Engine:
                self._h)
         return int(left.value), int(prom.value), st.as_dict()
 
+    def waitdie_carry(self, batch: EpochBatch, ts, rc, pos, revive=None, src_in=None, fresh=None, fresh_ts=None,
+                      fresh_src_base: int = 0, cap_txn=None, cap_nnz=None, out=None):
+        """The next WAIT_DIE population where the batch lives (dcc_waitdie_carry):
+        the txns that are not WD_GONE, and the GONE ones with revive[i] != 0 as
+        (WD_RUN, 0), in index order, then the txns of `fresh` as (WD_RUN, 0) with
+        fresh_ts and src = fresh_src_base + j.  Returns (EpochBatch, ts, rc, pos,
+        src, kept, stats), the arrays cut to the output's size, numpy for a host
+        batch and device tensors for a device batch; kept = the stayers.  `out`
+        is an EpochBatch with room (wide keys), its per-txn arrays in
+        out.meta["ts" / "rc" / "pos" / "src"] (allocated when absent); out=None
+        allocates room for cap_txn txns / cap_nnz accesses (default: both
+        batches whole).  A result that does not fit raises DccError(DCC_ERANGE)
+        with (n, nnz, kept) it needed in .needed."""
+        what = "waitdie_carry"
+        n, m = batch.n_txn, batch.nnz
+        dev = batch.on_device
+        nf = fresh.n_txn if fresh is not None else 0
+        mf = fresh.nnz if fresh is not None else 0
+        if fresh is not None and fresh.on_device != dev:
+            raise TypeError(f"{what}: batch and fresh must both be host or both be device batches")
+        if dev:
+            import torch
+            d = batch.offsets.device
+
+            def empty(k, wide):
+                return torch.empty(max(k, 1), dtype={8: torch.int64, 4: torch.int32, 1: torch.uint8}[wide], device=d)
+        else:
+            def empty(k, wide):
+                return np.empty(max(k, 1), {8: np.uint64, 4: np.uint32, 1: np.uint8}[wide])
+        keep = []
+
+        def arr(name, a, size, dt, need):
+            if a is None:
+                return None
+            if dev:
+                if not _is_device(a):
+                    raise TypeError(f"{what}: a device batch takes a device {name} tensor")
+                if not a.is_contiguous():
+                    raise ValueError(f"{what}: {name} must be contiguous")
+            else:
+                a = np.ascontiguousarray(a, dt)
+            if _itemsize(a) != size or a.shape[0] < need:
+                raise ValueError(f"{what}: {name} must hold {need} {size}-byte items")
+            keep.append(a)
+            # an empty array has no address: any non-null pointer stands for it
+            return _ptr(a) if a.shape[0] else _ptr(batch.offsets)
+
+        p_ts, p_rc, p_pos = (arr("ts", ts, 8, np.uint64, n), arr("rc", rc, 1, np.uint8, n),
+                             arr("pos", pos, 4, np.uint32, n))
+        p_rev, p_src = arr("revive", revive, 1, np.uint8, n), arr("src_in", src_in, 4, np.uint32, n)
+        p_fts = arr("fresh_ts", fresh_ts, 8, np.uint64, nf)
+        if out is None:
+            ct = n + nf if cap_txn is None else int(cap_txn)
+            cm = m + mf if cap_nnz is None else int(cap_nnz)
+            out = EpochBatch(empty(ct + 1, 4), empty(cm, 8), empty(cm, 1))
+            out.meta["cap"] = (ct, cm)
+        if _itemsize(out.offsets) != 4 or _itemsize(out.keys) != 8 or _itemsize(out.acctype) != 1:
+            raise TypeError(f"{what}: out holds u32 offsets, u64 keys and u8 access types")
+        ct, cm = out.meta.get("cap", (int(out.offsets.shape[0]) - 1,
+                                      min(int(out.keys.shape[0]), int(out.acctype.shape[0]))))
+        per = {}
+        for name, wide in (("ts", 8), ("rc", 1), ("pos", 4), ("src", 4)):
+            a = out.meta.get(name)
+            if a is None:
+                a = out.meta[name] = empty(ct, wide)
+            if _itemsize(a) != wide or a.shape[0] < ct:
+                raise ValueError(f"{what}: out.meta[{name!r}] must hold cap_txn {wide}-byte items")
+            per[name] = a
+        so = _abi.SelectOut(ct, cm, 0, 0, _ptr(out.offsets), _ptr(out.keys), _ptr(out.acctype), None, None, None,
+                            _ptr(per["src"]))
+        b = batch.to_c()
+        fb = fresh.to_c() if fresh is not None else None
+        a = _abi.WaitdieCarryArgs(C.pointer(b), p_ts, p_rc, p_pos, p_rev, p_src,
+                                  C.pointer(fb) if fb is not None else None, p_fts, int(fresh_src_base),
+                                  C.pointer(so), _ptr(per["ts"]), _ptr(per["rc"]), _ptr(per["pos"]))
+        st = _abi.Stats()
+        nt, mt, nk = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        code = lib.dcc_waitdie_carry(self._h, C.byref(a), C.byref(nt), C.byref(mt), C.byref(nk), C.byref(st))
+        try:
+            _check(code, self._h)
+        except DccError as e:
+            e.needed = (int(nt.value), int(mt.value), int(nk.value))
+            raise
+        tn, tm = int(nt.value), int(mt.value)
+        got = EpochBatch(out.offsets[:tn + 1], out.keys[:tm], out.acctype[:tm], None, None, None,
+                         {k: v[:tn] for k, v in per.items()})
+        return got, per["ts"][:tn], per["rc"][:tn], per["pos"][:tn], per["src"][:tn], int(nk.value), st.as_dict()
+
     # ------------------------------------------------------------- MVCC
     def mvcc_validate_epoch(self, batch: EpochBatch, ts, want_conflict: bool = True, want_vts: bool = True,
                             out_rc=None, out_conflict=None, out_vts=None):
@@ -1224,6 +1312,12 @@ def tso_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
 
 def waitdie_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
     return int(lib.dcc_waitdie_alg_bytes(n_txn, nnz, int(with_conflict)))
+
+
+def waitdie_carry_alg_bytes(n_txn: int, n_kept: int, nnz_kept: int, n_fresh: int = 0, nnz_fresh: int = 0,
+                            with_revive: bool = False, with_src: bool = True) -> int:
+    return int(lib.dcc_waitdie_carry_alg_bytes(n_txn, n_kept, nnz_kept, n_fresh, nnz_fresh, int(with_revive),
+                                               int(with_src)))
 
 
 def mvcc_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True, with_vts: bool = True) -> int:

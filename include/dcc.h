@@ -707,6 +707,83 @@ int dcc_waitdie_release(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts
  * least owner ts, largest waiter ts) + 5N (rc, pos out) [+ 4N conflict]. */
 uint64_t dcc_waitdie_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
 
+/* dcc_waitdie_carry.  The population of the next epoch, where the batch lives:
+ * the stayers followed by the fresh txns.  A stayer is a txn with rc != GONE,
+ * or a GONE txn with revive[i] != 0.  Stayers keep their index order; each is
+ * written with its accesses in list order and its ts, rc, pos and src
+ * (src_in[i], or i when src_in is NULL, so identities compose over any number
+ * of carries); a revived txn is written as (RUN, 0) with the ts it keeps
+ * (worker_thread.cpp:478).  The fresh txns keep their order behind the stayers,
+ * each as (RUN, 0) with its fresh_ts and src = fresh_src_base + j.  *out_kept
+ * (host, may be NULL) = the stayers, *out_n / *out_nnz (host, may be NULL) =
+ * the txns / accesses of the output.  Nothing of the input is written; the
+ * output arrays must not overlap the inputs.
+ *
+ * The call changes no decision.  A GONE txn has no trace (above), so dropping
+ * it removes nothing an epoch or a release reads; the relative index order of
+ * all others is preserved, so the order the RUN txns run in and the waiter
+ * queues' ties (lower index nearer the head) do not move: epochs and releases
+ * on the carried population decide, txn for txn through src, what they decide
+ * on the population that was never compacted.  A revived txn keeps its place
+ * among the stayers: the reference restarts an aborted txn at an arbitrary
+ * later time (system/abort_queue.cpp), so this is one of its interleavings.
+ * A died txn that still owns a prefix is not GONE and is simply kept.
+ *
+ * Txn length is not limited (the call moves data) and zero-length txns are
+ * kept; the epoch rejects what it rejects.  batch and fresh must agree on
+ * DCC_DEVICE_PTRS: with it every array of the call is device memory, without
+ * it host memory.  Either batch may be in any compact form, independently
+ * (DCC_KEYS_U32, DCC_ACCTYPE_2BIT; start_tn / finish_tn / order are ignored);
+ * the output is always wide.
+ * DCC_EINVAL, nothing written: NULL a, batch, out, ts, rc, pos, out_ts, out_rc
+ * or out_pos; fresh without fresh_ts; batch and fresh disagreeing on
+ * DCC_DEVICE_PTRS; out->txn_base or out->nnz_base not 0; malformed offsets of
+ * either batch (checked on the device before anything indexes with them); an
+ * rc byte outside the five states; for a txn that is not GONE pos > len, RCOK
+ * with pos != len, WAIT with pos >= len (the rules of the epoch, so an
+ * accepted output is a state the epoch accepts) or revive[i] != 0.
+ * DCC_ERANGE, nothing written to any output array: stayers + fresh exceed
+ * out->cap_txn or out->cap_nnz, or the accesses do not fit a uint32_t; *out_n /
+ * *out_nnz / *out_kept then report what was needed.
+ * Local: no collective.  A dcc_init_multi context runs it on rank 0's GPU, a
+ * context with a communicator as any other; pipelined OCC epochs in flight
+ * complete first.  dcc_reserve covers its workspaces: a warmed-up call on a
+ * device population allocates nothing.
+ * Stats: n_commit = stayers, n_abort = dropped, n_survivors = revived,
+ * alg_bytes (dcc_waitdie_carry_alg_bytes), device_ms, total_ms; with profiling
+ * phase_ms: 0 = count + state check, 1 = scan, 2 = stayers' scatter, 3 = fresh
+ * append. */
+struct dcc_select_out; /* the select's output CSR, below */
+typedef struct dcc_waitdie_carry_args {
+  const dcc_batch* batch;     /* the current population; n_txn may be 0                    */
+  const uint64_t* ts;         /* [n_txn]                                                   */
+  const uint8_t*  rc;         /* [n_txn] the five WAIT_DIE states                          */
+  const uint32_t* pos;        /* [n_txn]                                                   */
+  const uint8_t*  revive;     /* [n_txn] or NULL: a GONE txn with revive[i] != 0 re-enters
+                                 as (DCC_WD_RUN, 0) with its ts                            */
+  const uint32_t* src_in;     /* [n_txn] or NULL (identity): composes like the select's    */
+  const dcc_batch* fresh;     /* new arrivals, appended behind the stayers; or NULL        */
+  const uint64_t* fresh_ts;   /* [fresh->n_txn]                                            */
+  uint32_t fresh_src_base;    /* src of fresh txn j = fresh_src_base + j                   */
+  const struct dcc_select_out* out; /* CSR (always wide) + src; txn_base and nnz_base
+                                 must be 0; start_tn / finish_tn / order are not written              */
+  uint64_t* out_ts; uint8_t* out_rc; uint32_t* out_pos;   /* [out->cap_txn]                */
+} dcc_waitdie_carry_args;
+int dcc_waitdie_carry(dcc_ctx* ctx, const dcc_waitdie_carry_args* a, uint64_t* out_n,
+                      uint64_t* out_nnz, uint64_t* out_kept, dcc_stats* out_stats);
+/* Algorithmic bytes of one carry:
+ *   offsets, rc and revive of the input, read    4(n_txn+1) + n_txn(1 + with_revive)
+ *   per stayer: ts and pos read (12 B), ts, rc,
+ *   pos written (13 B)                           25 n_kept
+ *   stayers' accesses (key + type, read+written) 18 nnz_kept
+ *   fresh offsets and ts read                    4(n_fresh+1) + 8 n_fresh
+ *   fresh ts, rc, pos written                    13 n_fresh
+ *   fresh accesses                               18 nnz_fresh
+ *   output offsets written                       4(n_kept + n_fresh + 1)
+ *   src, when with_src                           8 n_kept + 4 n_fresh */
+uint64_t dcc_waitdie_carry_alg_bytes(uint64_t n_txn, uint64_t n_kept, uint64_t nnz_kept,
+                                     uint64_t n_fresh, uint64_t nnz_fresh, int with_revive, int with_src);
+
 /* ------------------------------ NO_WAIT lock table that lives across epochs */
 /* Row_lock's NO_WAIT state where the batches live: a device-resident map
  * row -> (lock_type, owner_cnt) that epochs acquire into and finished txns
