@@ -475,7 +475,8 @@ struct dcc_ctx {
   int calvin_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint32_t* out_group,
                    uint8_t* out_rc, uint32_t* out_wave, dcc_stats* st);
   // NO_WAIT 2PL (nowait.hip)
-  int nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict);
+  // whole_table: room in `table` for every request (a key-sharded epoch sizes its own)
+  int nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict, bool whole_table = true);
   // lt: the epoch runs against this lock table and leaves its grants in it
   int nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
                    uint32_t* out_conflict, dcc_stats* st, dcc_locktab* lt = nullptr);
@@ -560,6 +561,10 @@ struct dcc_ctx {
   int carry_reserve(uint64_t n, uint64_t nnz);
   int waitdie_carry(const dcc_waitdie_carry_args* a, uint64_t* out_n, uint64_t* out_nnz, uint64_t* out_kept,
                     dcc_stats* st);
+  // key-sharded NO_WAIT epoch (nowait.hip): a status byte per txn (the rounds'
+  // exchange, then 64 - the conflict ordinal); a multi-GPU context's per-rank
+  // conflict ordinals of a device batch
+  DevBuf nw_stat, sh_conf;
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes
@@ -616,6 +621,8 @@ int dcc_multi_occ_epoch(dcc_ctx* ctx, const dcc_batch* b, uint8_t* out_rc, uint6
                         dcc_stats* st);
 int dcc_multi_calvin_epoch(dcc_ctx* ctx, const dcc_batch* b, const dcc_calvin_held* held,
                            uint32_t* out_group, uint8_t* out_rc, uint32_t* out_wave, dcc_stats* st);
+int dcc_multi_nowait_epoch(dcc_ctx* ctx, const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
+                           uint32_t* out_conflict, dcc_stats* st);
 int dcc_multi_each(dcc_ctx* ctx, int (*fn)(dcc_ctx*, void*), void* user);
 int dcc_multi_occ_snapshot(dcc_ctx* ctx, const dcc_batch* b, const dcc_occ_snapshot* snap,
                            uint8_t* out_rc, dcc_stats* st);

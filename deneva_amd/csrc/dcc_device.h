@@ -85,6 +85,15 @@ __device__ __host__ inline uint32_t fmix32(uint32_t h) {
   return h;
 }
 
+// dcc_key_shard (shard.cpp) on the device: splitmix64 finaliser, multiply-high
+__device__ inline uint32_t key_shard(uint64_t key, uint32_t nranks) {
+  uint64_t x = (key ^ 0x5DEECE66Dull) + 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return (uint32_t)__umul64hi(x, (uint64_t)nranks);
+}
+
 // Probe sequence: double hashing.  The home slot keeps the low 32 key bits
 // (offset by a hash of the high bits), so the dense, zipf-hot low rows of a
 // table (YCSB row ids, TPC-C warehouse/district/customer keys under their

@@ -335,6 +335,70 @@ int dcc_multi_occ_epoch(dcc_ctx* ctx, const dcc_batch* b, uint8_t* out_rc, uint6
   return DCC_OK;
 }
 
+// NO_WAIT lock epoch, key-sharded (nowait.hip): every rank
+// takes the whole batch and the whole held list with DCC_SHARD_SELF, keeps the
+// rows of its key shard in its own lock table and returns the whole outputs,
+// which the rounds' exchanges keep identical.  The host-side checks run here;
+// the device check of offsets, lengths and keys runs on every rank over the
+// whole batch before its first collective, so the ranks reject a malformed
+// batch alike and none waits for another.
+int dcc_multi_nowait_epoch(dcc_ctx* ctx, const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
+                           uint32_t* out_conflict, dcc_stats* st) {
+  if (!b) return ctx->fail(DCC_EINVAL, "null batch");
+  if (!out_rc) return ctx->fail(DCC_EINVAL, "nowait: null out_rc");
+  if (int e = ctx->check_batch(b, false)) return e;  // offsets and lengths: on the device, as on one GPU
+  if (held && held->n && (!held->keys || !held->acctype))
+    return ctx->fail(DCC_EINVAL, "nowait: null held keys/acctype");
+  const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
+  const uint64_t n = b->n_txn;
+  const int R = (int)ctx->multi->sub.size();
+  if (n == 0) {
+    if (st) {
+      memset(st, 0, sizeof *st);
+      st->n_shards = (uint32_t)R;
+    }
+    return DCC_OK;
+  }
+  std::vector<std::vector<uint8_t>> rc(R);
+  std::vector<std::vector<uint32_t>> cf(R);
+  std::vector<dcc_stats> S(R);
+  const int e = run_ranks(ctx, [&](int r, dcc_ctx* s) -> int {
+    dcc_batch fb = *b;
+    fb.flags |= DCC_SHARD_SELF;
+    if (!dev) {  // host outputs: every rank's, compared below
+      rc[r].resize(n);
+      if (out_conflict) cf[r].resize(n);
+      return s->nowait_epoch(&fb, held, rc[r].data(), out_conflict ? cf[r].data() : nullptr, &S[r]);
+    }
+    int x = DCC_OK;
+    if ((x = s->sh_rc.ensure(s, n + 16, "shard rc")) != DCC_OK) return x;
+    if (out_conflict && (x = s->sh_conf.ensure(s, n * 4 + 16, "shard conflicts")) != DCC_OK) return x;
+    uint8_t* drc = (uint8_t*)s->sh_rc.p;
+    uint32_t* dcf = out_conflict ? (uint32_t*)s->sh_conf.p : nullptr;
+    if ((x = s->nowait_epoch(&fb, held, drc, dcf, &S[r])) != DCC_OK) return x;
+    hipError_t he = hipSuccess;
+    if (r == 0) {  // the caller's device arrays (this GPU or a peer)
+      he = hipMemcpy(out_rc, drc, n, hipMemcpyDeviceToDevice);
+      if (he == hipSuccess && dcf) he = hipMemcpy(out_conflict, dcf, n * 4, hipMemcpyDeviceToDevice);
+    }
+    return he == hipSuccess ? DCC_OK : s->hip_fail(he, "multi-GPU nowait: decisions out");
+  });
+  if (e != DCC_OK) return e;
+  if (!dev) {
+    for (int r = 1; r < R; r++)
+      if (memcmp(rc[r].data(), rc[0].data(), n) != 0 ||
+          (out_conflict && memcmp(cf[r].data(), cf[0].data(), n * 4) != 0))
+        return ctx->fail(DCC_EIO, "multi-GPU nowait: ranks 0 and %d decided differently", r);
+    memcpy(out_rc, rc[0].data(), n);
+    if (out_conflict) memcpy(out_conflict, cf[0].data(), n * 4);
+  }
+  if (st) {  // every rank counts the whole batch
+    *st = S[0];
+    for (int r = 1; r < R; r++) st->device_ms = std::max(st->device_ms, S[r].device_ms);
+  }
+  return DCC_OK;
+}
+
 int dcc_multi_calvin_epoch(dcc_ctx* ctx, const dcc_batch* b, const dcc_calvin_held* held,
                            uint32_t* out_group, uint8_t* out_rc, uint32_t* out_wave,
                            dcc_stats* st) {

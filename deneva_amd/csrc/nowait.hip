@@ -36,15 +36,37 @@
 //           k_nw_publish the next round's words of the txns still undecided
 //           k_nw_retag   round tags exhausted: drop every tagged word
 //           k_nw_final   RC bytes, counts, first conflicting request
+//
+// Key-sharded (DCC_SHARD_SELF on a context with a communicator; DESIGN.md
+// §8p): every rank holds the whole batch and the whole held list, and rank r
+// enters only the rows with dcc_key_shard(key, R) == r into its table, which
+// is sized from its own requests and held rows (k_nw_count).  A request of
+// another rank's row carries SID_REMOTE in sid[] and takes no part in any
+// pass of this rank.  The kernels are the SH instantiations of the ones
+// above; a round splits k_nw_decide in two around the exchange:
+//           NW_EVAL      the rank's accesses of every undecided txn into one
+//                        status byte per txn (0 none, 1 blocked, 2 killed)
+//           byte-MAX all-reduce of the n status bytes
+//           NW_APPLY     state from the reduced byte (the same on every rank),
+//                        tag-0 words of the commits on this rank's rows,
+//                        the blocked txns to the next list
+// A txn that names a row twice with EX on either side is found by the row's
+// rank, which marks its status byte killed in the build; the other ranks
+// learn of it in round 1's exchange.  Their round-1 words of that txn block
+// its readers for that one round and carry a stale tag from round 2 on.
+// After the fixed point each rank's first conflicting request goes through
+// one more byte-MAX exchange as 64 - ordinal (k_nw_final, k_nw_conf).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <type_traits>
 
 #include "dcc.h"
 #include "dcc_ctx.h"
 #include "dcc_device.h"
+#include "dcc_scan.h"
 #include "nowait_lanes.h"
 #include "occ_kernels.h"
 #include "seg_rounds.h"
@@ -58,10 +80,23 @@ constexpr uint32_t NW_STAGE = 1024;   // blocked txns a workgroup stages before 
 constexpr uint32_t NW_ERR_FULL = 4, NW_ERR_STATE = 8;
 // counter words (nw_misc) next to SEG_C_ERR / SEG_C_MAXLEN; the ring holds the list lengths
 constexpr uint32_t NW_C_NEX = 2, NW_C_RO = 3, NW_C_COMMIT = 4, NW_C_RING = 8, NW_C_WORDS = NW_C_RING + SEG_RING;
+// key-sharded: the rank's own requests / held rows, the reserved key in the held list
+constexpr uint32_t NW_C_OWN = 5, NW_C_OWNHELD = 6, NW_ERR_HKEY = 16;
+// sid[] of a request whose row another rank owns (SID_NONE: table full)
+constexpr uint32_t SID_REMOTE = SID_NONE - 1;
+// status bytes of a sharded round
+constexpr uint8_t NW_S_BLOCKED = 1, NW_S_KILLED = 2;
+
+// the request has a slot in this rank's table
+template <bool SH>
+__device__ inline bool has_slot(uint32_t s) {
+  return SH ? s < SID_REMOTE : s != SID_NONE;
+}
 
 // A txn names a row twice with EX on either side (NO_WAIT keeps no owner
 // list, row_lock.cpp:176-182): the lanes of the later requests.  Rows compare
 // by slot id (one slot per key).  Every lane of the wave calls it.
+template <bool SH>
 __device__ inline bool self_conflict(const Seg& g, uint32_t lp, bool v, uint32_t s, uint32_t ex) {
   bool sc = false;
   const uint32_t P = 1u << lp;
@@ -69,14 +104,53 @@ __device__ inline bool self_conflict(const Seg& g, uint32_t lp, bool v, uint32_t
     if (!ballot64(v && g.a > q)) break;  // no lane of the wave has an earlier access q
     const uint32_t so = __shfl(s, (int)(g.seg0 + q));
     const uint32_t eo = __shfl(ex, (int)(g.seg0 + q));
-    if (v && q < g.a && so == s && s != SID_NONE && (ex | eo)) sc = true;
+    if (v && q < g.a && so == s && has_slot<SH>(s) && (ex | eo)) sc = true;
   }
   return sc;
 }
 
+// The rows a rank keeps: all of them, or its key shard.
+struct NwAll {};
+struct NwOwn {
+  uint32_t rank, R;
+};
+template <bool SH>
+using NwWho = std::conditional_t<SH, NwOwn, NwAll>;
+template <bool SH>
+__device__ inline bool owns(const NwWho<SH>& w, uint64_t key) {
+  if constexpr (SH) return key_shard(key, w.R) == w.rank;
+  else return true;
+}
+
+// Key-sharded: the rank's own requests and held rows (its table's size), and
+// the reserved key anywhere in the held list.  Every index is below nnz / hn:
+// it runs next to the batch check, before the offsets are known to be sound.
+__global__ __launch_bounds__(CHK_T) void k_nw_count(const uint64_t* __restrict__ keys, uint64_t nnz,
+                                                    const uint64_t* __restrict__ hkeys, uint64_t hn, NwOwn w,
+                                                    uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t s_a[CHK_T / 64], s_b[CHK_T / 64];
+  const uint64_t tid = (uint64_t)blockIdx.x * CHK_T + threadIdx.x, stride = (uint64_t)gridDim.x * CHK_T;
+  uint32_t own = 0, ownh = 0;
+  bool bad = false;
+  for (uint64_t x = tid; x < nnz; x += stride) own += owns<true>(w, keys[x]) ? 1u : 0u;
+  for (uint64_t x = tid; x < hn; x += stride) {
+    const uint64_t key = hkeys[x];
+    bad |= key == KEY_EMPTY;
+    ownh += owns<true>(w, key) ? 1u : 0u;
+  }
+  if (bad) atomicOr(&cnt[SEG_C_ERR], NW_ERR_HKEY);
+  own = block_reduce<CHK_T / 64, AddOp<uint32_t>>(own, s_a);
+  ownh = block_reduce<CHK_T / 64, AddOp<uint32_t>>(ownh, s_b);
+  if (threadIdx.x == 0) {
+    if (own) atomicAdd(&cnt[NW_C_OWN], own);
+    if (ownh) atomicAdd(&cnt[NW_C_OWNHELD], ownh);
+  }
+}
+
+template <bool SH>
 __global__ __launch_bounds__(NW_T) void k_nw_held(const uint64_t* __restrict__ keys,
                                                   const uint8_t* __restrict__ at, uint64_t n, Slot* tab,
-                                                  uint32_t mask, uint32_t* __restrict__ cnt) {
+                                                  uint32_t mask, uint32_t* __restrict__ cnt, NwWho<SH> who) {
   const uint64_t stride = (uint64_t)gridDim.x * NW_T;
   for (uint64_t x = (uint64_t)blockIdx.x * NW_T + threadIdx.x; x < n; x += stride) {
     const uint64_t key = keys[x];
@@ -84,6 +158,7 @@ __global__ __launch_bounds__(NW_T) void k_nw_held(const uint64_t* __restrict__ k
       atomicOr(&cnt[SEG_C_ERR], CHK_ERR_KEY);
       continue;
     }
+    if (!owns<SH>(who, key)) continue;
     const uint32_t s = table_insert(tab, mask, key);
     if (s == SID_NONE) {
       atomicOr(&cnt[SEG_C_ERR], NW_ERR_FULL);
@@ -106,8 +181,15 @@ struct NwArgs {
   uint8_t* state;
   uint32_t* cnt;
 };
+struct NwShArgs : NwArgs {
+  NwOwn who;
+  uint8_t* stat;  // [n] the round's status bytes, then 64 - the conflict ordinal
+};
+template <bool SH>
+using NwA = std::conditional_t<SH, NwShArgs, NwArgs>;
 
-__global__ __launch_bounds__(NW_T) void k_nw_build(NwArgs A) {
+template <bool SH>
+__global__ __launch_bounds__(NW_T) void k_nw_build(NwA<SH> A) {
   __shared__ uint32_t s_ro, s_nex;
   if (threadIdx.x == 0) {
     s_ro = 0;
@@ -130,20 +212,28 @@ __global__ __launch_bounds__(NW_T) void k_nw_build(NwArgs A) {
     uint32_t ex = 0, s = SID_NONE;
     if (v) {
       ex = is_ex(A.at[x]);
-      s = table_insert(A.tab, A.mask, A.keys[x]);
+      const uint64_t key = A.keys[x];
+      bool mine = true;
+      if constexpr (SH) mine = owns<true>(A.who, key);
+      s = mine ? table_insert(A.tab, A.mask, key) : SID_REMOTE;
       A.sid[x] = s;
       if (s == SID_NONE) atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_FULL);
     }
-    const bool sc = self_conflict(g, A.lp, v, s, ex);
+    const bool sc = self_conflict<SH>(g, A.lp, v, s, ex);
     const bool selfc = (ballot64(sc) & g.mask) != 0;
     const uint64_t exb = ballot64(v && ex) & g.mask;
-    if (v && !selfc && s != SID_NONE) {
+    if (v && !selfc && has_slot<SH>(s)) {
       const uint32_t w = own_word(round_tag(1), (uint32_t)t + 1u);
       own_min(&A.tab[s].own, w);
       if (ex) own_min(&A.tab[s].aux, w);
     }
     if (tv && g.a == 0) {
-      A.state[t] = selfc ? ST_ABORT : ST_UNDECIDED;  // an aborted txn publishes nothing
+      if constexpr (SH) {  // the state bytes stay equal on every rank: round 1's exchange carries the abort
+        A.state[t] = ST_UNDECIDED;
+        if (selfc) A.stat[t] = NW_S_KILLED;
+      } else {
+        A.state[t] = selfc ? ST_ABORT : ST_UNDECIDED;  // an aborted txn publishes nothing
+      }
       ro += exb ? 0u : 1u;
       nex += (uint32_t)__popcll(exb);
     }
@@ -162,9 +252,17 @@ __global__ __launch_bounds__(NW_T) void k_nw_build(NwArgs A) {
 // atomic per NW_STAGE of them (the list order is free: decisions do not
 // depend on it).  A commit publishes its tag-0 words right away: a reader
 // that sees one early is killed by a txn that does kill it.
-__global__ __launch_bounds__(NW_T) void k_nw_decide(NwArgs A, uint32_t tag, const uint32_t* __restrict__ list,
+// Key-sharded the round is two launches around the exchange: NW_EVAL leaves
+// the status byte of every txn it finds blocked or killed on this rank's rows
+// (the bytes are clear before it; a txn the build marked is left alone),
+// NW_APPLY takes the reduced byte in place of the ballots and clears it.
+constexpr int NW_ONE = 0, NW_EVAL = 1, NW_APPLY = 2;
+template <int MODE>
+__global__ __launch_bounds__(NW_T) void k_nw_decide(NwA<MODE != NW_ONE> A, uint32_t tag,
+                                                    const uint32_t* __restrict__ list,
                                                     const uint32_t* __restrict__ m_in,
                                                     uint32_t* __restrict__ list_out, uint32_t* m_out) {
+  constexpr bool SH = MODE != NW_ONE;
   __shared__ uint32_t l_buf[NW_STAGE];
   __shared__ uint32_t l_cnt, l_base;
   if (threadIdx.x == 0) l_cnt = 0;
@@ -189,6 +287,7 @@ __global__ __launch_bounds__(NW_T) void k_nw_decide(NwArgs A, uint32_t tag, cons
     if (ev) {
       t = list ? list[e] : (uint32_t)e;
       act = A.state[t] == ST_UNDECIDED;
+      if constexpr (MODE == NW_EVAL) act = act && (list || A.stat[t] == 0);
     }
     uint32_t o0 = 0, len = 0;
     if (act) {
@@ -198,14 +297,30 @@ __global__ __launch_bounds__(NW_T) void k_nw_decide(NwArgs A, uint32_t tag, cons
     const bool v = act && g.a < len;
     const uint64_t x = (uint64_t)o0 + g.a;
     uint32_t ex = 0, s = SID_NONE, ps = 0;
-    if (v) {
-      ex = is_ex(A.at[x]);
-      s = A.sid[x];
-      if (s != SID_NONE) ps = own_status(ex ? A.tab[s].own : A.tab[s].aux, tag, t + 1u);
+    bool killed, blocked;
+    if constexpr (MODE == NW_APPLY) {
+      const uint32_t sb = act ? A.stat[t] : 0u;  // every lane of the txn, before its lead clears the byte
+      killed = sb == NW_S_KILLED;
+      blocked = sb == NW_S_BLOCKED;
+      if (v && sb == 0) {
+        ex = is_ex(A.at[x]);
+        s = A.sid[x];
+      }
+      if (act && g.a == 0 && sb) A.stat[t] = 0;
+    } else {
+      if (v) {
+        ex = is_ex(A.at[x]);
+        s = A.sid[x];
+        if (has_slot<SH>(s)) ps = own_status(ex ? A.tab[s].own : A.tab[s].aux, tag, t + 1u);
+      }
+      killed = (ballot64(ps & PS_KILLED) & g.mask) != 0;
+      blocked = !killed && (ballot64(ps & PS_BLOCKED) & g.mask) != 0;
     }
-    const bool killed = (ballot64(ps & PS_KILLED) & g.mask) != 0;
-    const bool blocked = !killed && (ballot64(ps & PS_BLOCKED) & g.mask) != 0;
-    if (v && !killed && !blocked && s != SID_NONE) {  // commit: hold every lock to the end of the epoch
+    if constexpr (MODE == NW_EVAL) {
+      if (act && g.a == 0 && (killed || blocked)) A.stat[t] = killed ? NW_S_KILLED : NW_S_BLOCKED;
+      continue;
+    }
+    if (v && !killed && !blocked && has_slot<SH>(s)) {  // commit: hold every lock to the end of the epoch
       own_min(&A.tab[s].own, t + 1u);
       if (ex) own_min(&A.tab[s].aux, t + 1u);
     }
@@ -224,12 +339,13 @@ __global__ __launch_bounds__(NW_T) void k_nw_decide(NwArgs A, uint32_t tag, cons
     __syncthreads();  // every thread has read the count before the next step adds to it
     if (staged > NW_STAGE - NW_T) flush();  // the next step adds at most NW_T
   }
-  flush();
+  if constexpr (MODE != NW_EVAL) flush();
 }
 
 // The words of round `tag` for the txns still undecided (the list of the
 // round before).  Workgroup 0 clears the length word that round appends to.
-__global__ __launch_bounds__(NW_T) void k_nw_publish(NwArgs A, uint32_t tag, const uint32_t* __restrict__ list,
+template <bool SH>
+__global__ __launch_bounds__(NW_T) void k_nw_publish(NwA<SH> A, uint32_t tag, const uint32_t* __restrict__ list,
                                                      const uint32_t* __restrict__ m_in, uint32_t* m_zero) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *m_zero = 0;
   const Seg g = seg_of(A.lp);
@@ -243,7 +359,7 @@ __global__ __launch_bounds__(NW_T) void k_nw_publish(NwArgs A, uint32_t tag, con
     if (g.a >= len) continue;
     const uint64_t x = (uint64_t)o0 + g.a;
     const uint32_t s = A.sid[x];
-    if (s == SID_NONE) continue;
+    if (!has_slot<SH>(s)) continue;
     const uint32_t w = own_word(tag, t + 1u);
     own_min(&A.tab[s].own, w);
     if (is_ex(A.at[x])) own_min(&A.tab[s].aux, w);
@@ -263,7 +379,12 @@ __global__ __launch_bounds__(NW_T) void k_nw_retag(Slot* tab, uint64_t cap) {
 // lock_get returned Abort: the first that names a row again with EX on either
 // side, or that conflicts with a held row or with a committed txn below it
 // (the committed-only words: tag 0).
-__global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict__ rc,
+// Key-sharded: the first such access among this rank's rows, as 64 - its
+// ordinal in the whole txn (1 .. 64, MAX_TXN_LEN is 64; 0: none here) into the
+// status byte, whose byte-MAX over the ranks is the lowest ordinal
+// (k_nw_conf); `conflict` only says whether the ordinals are wanted.
+template <bool SH>
+__global__ __launch_bounds__(NW_T) void k_nw_final(NwA<SH> A, uint8_t* __restrict__ rc,
                                                    uint32_t* __restrict__ conflict) {
   __shared__ uint32_t s_commit;
   if (threadIdx.x == 0) s_commit = 0;
@@ -283,7 +404,10 @@ __global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict
     }
     if (!conflict) continue;
     if (!ballot64(ab)) {  // no aborted txn in the wave
-      if (tv && g.a == 0) conflict[t] = DCC_ACCESS_NONE;
+      if (tv && g.a == 0) {
+        if constexpr (SH) A.stat[t] = 0;
+        else conflict[t] = DCC_ACCESS_NONE;
+      }
       continue;
     }
     uint32_t o0 = 0, len = 0;
@@ -298,20 +422,24 @@ __global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict
     if (v) {
       ex = is_ex(A.at[x]);
       s = A.sid[x];
-      if (s != SID_NONE) {
+      if (has_slot<SH>(s)) {
         const uint32_t w = ex ? A.tab[s].own : A.tab[s].aux;
         c = (w >> IDX_BITS) == 0 && (w & IDX_MASK) < (uint32_t)t + 1u;
       }
     }
-    c = self_conflict(g, A.lp, v, s, ex) || c;
+    c = self_conflict<SH>(g, A.lp, v, s, ex) || c;
     const uint64_t cb = ballot64(c) & g.mask;
     if (tv && g.a == 0) {
-      uint32_t o = DCC_ACCESS_NONE;
-      if (ab) {
-        if (cb) o = (uint32_t)__builtin_ctzll(cb) - g.seg0;
-        else atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_STATE);  // aborted without a conflicting request
+      if constexpr (SH) {
+        A.stat[t] = ab && cb ? (uint8_t)(MAX_TXN_LEN - ((uint32_t)__builtin_ctzll(cb) - g.seg0)) : (uint8_t)0;
+      } else {
+        uint32_t o = DCC_ACCESS_NONE;
+        if (ab) {
+          if (cb) o = (uint32_t)__builtin_ctzll(cb) - g.seg0;
+          else atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_STATE);  // aborted without a conflicting request
+        }
+        conflict[t] = o;
       }
-      conflict[t] = o;
     }
   }
   if (commits) atomicAdd(&s_commit, commits);
@@ -319,16 +447,30 @@ __global__ __launch_bounds__(NW_T) void k_nw_final(NwArgs A, uint8_t* __restrict
   if (threadIdx.x == 0 && s_commit) atomicAdd(&A.cnt[NW_C_COMMIT], s_commit);
 }
 
+// Key-sharded: the conflict ordinals from the reduced bytes of k_nw_final.
+__global__ __launch_bounds__(NW_T) void k_nw_conf(uint64_t n, const uint8_t* __restrict__ state,
+                                                  const uint8_t* __restrict__ stat, uint32_t* __restrict__ conflict,
+                                                  uint32_t* __restrict__ cnt) {
+  const uint64_t stride = (uint64_t)gridDim.x * NW_T;
+  for (uint64_t t = (uint64_t)blockIdx.x * NW_T + threadIdx.x; t < n; t += stride) {
+    const uint32_t b = stat[t];
+    const bool ab = state[t] != ST_COMMIT;
+    if (ab && !b) atomicOr(&cnt[SEG_C_ERR], NW_ERR_STATE);  // aborted without a conflicting request on any rank
+    conflict[t] = ab && b ? MAX_TXN_LEN - b : DCC_ACCESS_NONE;
+  }
+}
+
 }  // namespace
 
-int dcc_ctx::nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict) {
+int dcc_ctx::nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict, bool whole_table) {
   CR(nw_misc.ensure(this, NW_C_WORDS * 4, "nowait counters"));
+  CR(nw_stat.ensure(this, n + 16, "nowait status bytes"));
   CR(nw_sid.ensure(this, std::max<uint64_t>(nnz, 1) * 4, "nowait slot ids"));
   CR(nw_list.ensure(this, 2 * std::max<uint64_t>(n, 1) * 4, "nowait undecided lists"));
   if (with_conflict) CR(nw_conf.ensure(this, std::max<uint64_t>(n, 1) * 4, "nowait conflicts"));
   CR(state.ensure(this, n + 16, "state"));
   CR(rc.ensure(this, n + 16, "rc"));
-  CR(table.ensure(this, table_capacity(nnz) * sizeof(Slot), "table"));
+  if (whole_table) CR(table.ensure(this, table_capacity(nnz) * sizeof(Slot), "table"));
   return DCC_OK;
 }
 
@@ -339,7 +481,11 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   dcc_stats& S = es.S;
   if (!out_rc) return fail(DCC_EINVAL, "nowait: null out_rc");
   CR(check_batch(b, false));  // the offsets are checked on the device (k_batch_check)
-  if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "nowait: single-GPU engine");
+  // key-sharded: the batch is the whole epoch on every rank (DCC_SHARD_SELF); a lock table is one GPU's
+  const bool sh = !lt && sharded() && (b->flags & DCC_SHARD_SELF) != 0;
+  if (comm_ranks() > 1 && !sh)
+    return fail(DCC_ENOTSUP, "nowait: more than one rank takes the whole epoch with DCC_SHARD_SELF and no lock table");
+  if (sh) S.n_shards = (uint32_t)comm_ranks();
   const uint64_t hn = held ? held->n : 0;
   if (lt && hn) return fail(DCC_EINVAL, "nowait: a held list next to a lock table");
   if (hn && (!held->keys || !held->acctype)) return fail(DCC_EINVAL, "nowait: null held keys/acctype");
@@ -353,27 +499,43 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   DevBatch d;
   CR(stage_batch(b, d));
   const uint64_t n = d.n, m = d.nnz;
-  const uint64_t cap = table_capacity(m + hn);
+  // key-sharded: the rank's own requests and held rows size the table, once they are counted below
+  uint64_t cap = sh ? 0 : table_capacity(m + hn);
   if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
-  const uint32_t mask = (uint32_t)(cap - 1);
-  CR(nowait_reserve(n, m, out_conflict != nullptr && !dev));
-  CR(table.ensure(this, cap * sizeof(Slot), "table"));
+  CR(nowait_reserve(n, m, out_conflict != nullptr && !dev, !sh));
+  if (!sh) CR(table.ensure(this, cap * sizeof(Slot), "table"));
   uint32_t* cnt = (uint32_t*)nw_misc.p;
   uint32_t* ring = cnt + NW_C_RING;
   uint32_t* lists[2] = {(uint32_t*)nw_list.p, (uint32_t*)nw_list.p + n};
   uint8_t* rc_dev = dev ? out_rc : (uint8_t*)rc.p;
   uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)nw_conf.p) : nullptr;
   const unsigned max_grid = (unsigned)n_cu * 16;
+  const NwOwn who{(uint32_t)comm_rank(), (uint32_t)comm_ranks()};
+  const uint64_t* hk = nullptr;
+  const uint8_t* ha = nullptr;
+  if (sh && hn) CR(stage_held(held, dev, hk, ha));
 
-  // reject a malformed batch before anything indexes with its offsets
+  // reject a malformed batch before anything indexes with its offsets (every
+  // rank checks the whole batch and the whole held list: all reject alike,
+  // before any collective)
   CK(hipMemsetAsync(cnt, 0, NW_C_WORDS * 4, stream));
   k_batch_check<false><<<launch_grid(std::max(n, m), CHK_T * 4, max_grid), CHK_T, 0, stream>>>(
       d.off, n, d.keys, m, cnt);
+  if (sh)
+    k_nw_count<<<launch_grid(std::max(m, hn), CHK_T * 4, max_grid), CHK_T, 0, stream>>>(d.keys, m, hk, hn, who, cnt);
   CK(hipGetLastError());
-  CK(hipMemcpyAsync(hmisc, cnt, 8, hipMemcpyDeviceToHost, stream));
+  CK(hipMemcpyAsync(hmisc, cnt, sh ? NW_C_RING * 4 : 8, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   BatchShape shape;
   CR(batch_checked(this, (const uint32_t*)hmisc, m, false, shape));
+  if (sh) {
+    const uint32_t* hc = (const uint32_t*)hmisc;
+    if (hc[SEG_C_ERR] & NW_ERR_HKEY) return fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
+    cap = table_capacity((uint64_t)hc[NW_C_OWN] + hc[NW_C_OWNHELD]);
+    if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
+    CR(table.ensure(this, cap * sizeof(Slot), "table"));
+  }
+  const uint32_t mask = (uint32_t)(cap - 1);
   const uint32_t lp = shape.lp;
   const uint64_t per_block = NW_T >> lp;  // txns per workgroup step
 
@@ -384,13 +546,21 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   Slot* tab = (Slot*)table.p;
   CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
   if (hn) {
-    const uint64_t* hk;
-    const uint8_t* ha;
-    CR(stage_held(held, dev, hk, ha));
-    k_nw_held<<<launch_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt);
+    if (sh) {
+      k_nw_held<true><<<launch_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt, who);
+    } else {
+      CR(stage_held(held, dev, hk, ha));
+      k_nw_held<false><<<launch_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt, NwAll{});
+    }
   }
   NwArgs A{n, d.off, d.keys, d.acctype, tab, mask, lp, (uint32_t*)nw_sid.p, (uint8_t*)state.p, cnt};
-  k_nw_build<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
+  NwShArgs AS{A, who, (uint8_t*)nw_stat.p};
+  if (sh) {
+    CK(hipMemsetAsync(AS.stat, 0, n, stream));  // every pass that sets a byte clears it again
+    k_nw_build<true><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(AS);
+  } else {
+    k_nw_build<false><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
+  }
   CK(hipGetLastError());
   // the table's held rows take the place of a held list: their tag-0 words
   LtEpoch L;
@@ -414,21 +584,47 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   // cleared (the whole ring is clear before round 1, which takes every txn and
   // clears nothing).  Rounds past the fixed point find empty lists.  `bound`
   // sizes the grids.
+  // Key-sharded, the state bytes and so the ring are the same on every rank:
+  // every rank enqueues the same rounds, the ones past the fixed point too,
+  // and each of them makes its one exchange.
   uint32_t rounds = 0;
-  CR(rounds_loop(this, ring, n, n + 2, "nowait", rounds,
-                 [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
-                   const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;  // tags 62 .. 1, then again
-                   const uint32_t tag = round_tag(er);
-                   const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
-                   const unsigned grid = launch_grid(bound, per_block, max_grid);
-                   if (r > 1) {
-                     if (er == 1)  // tag space exhausted: drop the tagged words, every undecided txn republishes
-                       k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
-                     k_nw_publish<<<grid, NW_T, 0, stream>>>(A, tag, lin, left, left_out);
-                   }
-                   k_nw_decide<<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
-                 }));
-  k_nw_final<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
+  if (sh) {
+    CR(rounds_loop(this, ring, n, n + 2, "nowait", rounds,
+                   [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) -> int {
+                     const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;
+                     const uint32_t tag = round_tag(er);
+                     const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
+                     const unsigned grid = launch_grid(bound, per_block, max_grid);
+                     if (r > 1) {
+                       if (er == 1) k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
+                       k_nw_publish<true><<<grid, NW_T, 0, stream>>>(AS, tag, lin, left, left_out);
+                     }
+                     k_nw_decide<NW_EVAL><<<grid, NW_T, 0, stream>>>(AS, tag, lin, left, nullptr, nullptr);
+                     CR(comm_allreduce_max_u8(AS.stat, n));
+                     k_nw_decide<NW_APPLY><<<grid, NW_T, 0, stream>>>(AS, tag, lin, left, lists[(r + 1) & 1], left_out);
+                     return DCC_OK;
+                   }));
+    k_nw_final<true><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(AS, rc_dev, conf_dev);
+    if (conf_dev) {  // the lowest conflicting ordinal over the ranks
+      CR(comm_allreduce_max_u8(AS.stat, n));
+      k_nw_conf<<<launch_grid(n, NW_T * 4, max_grid), NW_T, 0, stream>>>(n, A.state, AS.stat, conf_dev, cnt);
+    }
+  } else {
+    CR(rounds_loop(this, ring, n, n + 2, "nowait", rounds,
+                   [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
+                     const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;  // tags 62 .. 1, then again
+                     const uint32_t tag = round_tag(er);
+                     const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
+                     const unsigned grid = launch_grid(bound, per_block, max_grid);
+                     if (r > 1) {
+                       if (er == 1)  // tag space exhausted: drop the tagged words, every undecided txn republishes
+                         k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
+                       k_nw_publish<false><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, left_out);
+                     }
+                     k_nw_decide<NW_ONE><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
+                   }));
+    k_nw_final<false><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
+  }
   CK(hipGetLastError());
   if (lt) CR(locktab_grant(lt, L));  // the committed txns' requests stay in the table
   if (prof) CK(hipEventRecord(pev[4], stream));
@@ -469,7 +665,9 @@ extern "C" int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const
                                      uint8_t* out_rc, uint32_t* out_conflict, dcc_stats* out_stats) {
   if (!ctx || !batch || !out_rc) return DCC_EINVAL;
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
-  if (ctx->multi)  // the whole epoch on rank 0 (the lock table is one GPU's): no collective
+  if (ctx->multi && (batch->flags & DCC_SHARD_SELF) && dcc_multi_size(ctx) > 1)  // key-sharded over the ranks
+    return dcc_multi_nowait_epoch(ctx, batch, held, out_rc, out_conflict, out_stats);
+  if (ctx->multi)  // without the flag: the whole epoch on rank 0, no collective
     return dcc_multi_on_rank0(ctx, true, [&](dcc_ctx* s) {
       return s->nowait_epoch(batch, held, out_rc, out_conflict, out_stats);
     });

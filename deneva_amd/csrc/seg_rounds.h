@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "dcc.h"
 #include "dcc_ctx.h"
@@ -137,7 +138,8 @@ __global__ __launch_bounds__(SEG_AGG_T) void k_tile_aggscan(const typename Op::T
 // Several rounds are enqueued between host synchronisations -- 2, then
 // doubling up to DCC_OPT_BATCH_MAX and at most half the ring, so that no round
 // of a host batch clears a word the host has yet to read -- and rounds past
-// the fixed point return at once.  `rounds` is the first round that left no
+// the fixed point return at once.  An enqueue that returns int (one with a
+// collective in it) ends the call with its failure.  `rounds` is the first round that left no
 // txn undecided; past round `max_r` without one the call fails.  pev[2] is
 // recorded behind round 1, pev[3] at the end.
 template <class Enqueue>
@@ -152,7 +154,10 @@ int rounds_loop(dcc_ctx* ctx, uint32_t* ring, uint64_t n, uint64_t max_r, const 
   while (!done) {
     const uint32_t r0 = r;
     for (uint32_t q = 0; q < batch; q++, r++) {
-      enqueue(r, (const uint32_t*)&ring[r % SEG_RING], &ring[(r + 1) % SEG_RING], bound);
+      const uint32_t* left = &ring[r % SEG_RING];
+      uint32_t* left_out = &ring[(r + 1) % SEG_RING];
+      if constexpr (std::is_void_v<decltype(enqueue(r, left, left_out, bound))>) enqueue(r, left, left_out, bound);
+      else CR(enqueue(r, left, left_out, bound));
       if (prof && r == 1) CK(hipEventRecord(ctx->pev[2], stream));
     }
     CK(hipGetLastError());

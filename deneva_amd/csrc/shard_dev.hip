@@ -16,19 +16,13 @@
 
 #include "dcc.h"
 #include "dcc_ctx.h"
+#include "dcc_device.h"
 #include "dcc_scan.h"
 #include "radix_sort.h"
 
 namespace {
 
-// dcc_key_shard (shard.cpp) on the device: splitmix64 finaliser, multiply-high
-__device__ inline uint32_t key_shard(uint64_t key, uint32_t nranks) {
-  uint64_t x = (key ^ 0x5DEECE66Dull) + 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (uint32_t)__umul64hi(x, (uint64_t)nranks);
-}
+using dcc::key_shard;  // dcc_device.h
 
 constexpr uint32_t SH_B = 256;
 

@@ -464,12 +464,15 @@ class Engine:
 
     # ------------------------------------------------------ NO_WAIT (2PL)
     def nowait_lock_epoch(self, batch: EpochBatch, held=None, want_conflict: bool = True,
-                          out_rc=None, out_conflict=None):
+                          out_rc=None, out_conflict=None, shard: bool = False):
         """NO_WAIT lock acquisition of an epoch (dcc_nowait_lock_epoch): returns
         (rc u8[n], conflict u32[n] | None, stats).  held = (keys u64[h],
         acctype u8[h]): rows still locked by txns of earlier epochs.
         conflict[i] is the ordinal of the request an aborted txn aborted at,
-        ACCESS_NONE for a committed one."""
+        ACCESS_NONE for a committed one.  shard: on a multi-GPU engine or one
+        with a communicator the epoch is key-sharded across the ranks
+        (DCC_SHARD_SELF): every rank passes this whole batch and held list and
+        gets the whole outputs."""
         n = batch.n_txn
         dev = batch.on_device
         if dev:
@@ -489,7 +492,7 @@ class Engine:
         if out_rc.shape[0] < n or (out_conflict is not None and out_conflict.shape[0] < n):
             raise ValueError("nowait_lock_epoch: output buffer shorter than the epoch")
         st = _abi.Stats()
-        b = batch.to_c()
+        b = batch.to_c(_abi.SHARD_SELF if shard else 0)
         h = None
         if held is not None:
             hk, ha = held

@@ -92,7 +92,10 @@ extern "C" {
  * (one fixed-size all-gather per sweep level, no host synchronisation between
  * levels).  Without the flag a rank passes only its own accesses
  * (dcc_shard_filter) and the ranks exchange the serial ranges' records.
- * A multi-GPU context (dcc_init_multi) always shards this way. */
+ * A multi-GPU context (dcc_init_multi) always shards this way.
+ * dcc_nowait_lock_epoch takes the flag too (its comment has the contract):
+ * without it that call is not key-sharded at all.  On a context that is not
+ * key-sharded the flag is ignored. */
 #define DCC_SHARD_SELF 0x80u
 
 /* One epoch as a CSR of per-transaction access lists in capture order
@@ -464,8 +467,31 @@ int dcc_calvin_order_epoch_held(dcc_ctx* ctx, const dcc_batch* batch, const dcc_
  * start_tn / finish_tn / order of the batch are ignored.  With DCC_DEVICE_PTRS
  * the batch, the held arrays and the outputs are device memory.  The lock
  * table lives for the call only: the caller carries held rows from one epoch
- * to the next.  One GPU: a dcc_init_multi context runs the epoch on rank 0; a
- * communicator of more than one rank is DCC_ENOTSUP.
+ * to the next.  Without DCC_SHARD_SELF in batch->flags the epoch is one GPU's:
+ * a dcc_init_multi context runs it on rank 0, a communicator of more than one
+ * rank is DCC_ENOTSUP.
+ * With DCC_SHARD_SELF the epoch is key-sharded over the ranks of the context's
+ * communicator (dcc_comm_init, dcc_comm_init_host, the one-rank RCCL clique of
+ * DCC_OPT_COMM_SOLO) or the sub-contexts of a dcc_init_multi context.  Every
+ * rank passes the same whole batch and the same whole held list, with the same
+ * out_conflict choice; rank r keeps the rows with dcc_key_shard(key, R) == r,
+ * held rows included, in a lock table sized from its own requests and held
+ * rows.  Every rank returns the whole out_rc / out_conflict, identical on all
+ * ranks and equal to the one-GPU epoch's.  The call is a collective: one
+ * byte-MAX all-reduce of n_txn bytes per round enqueued and one more for
+ * out_conflict; every rank checks the whole batch and the whole held list
+ * before its first, so a malformed epoch is DCC_EINVAL on every rank alike.
+ * A dcc_init_multi context runs one host thread per rank, returns rank 0's
+ * outputs (host outputs: after comparing every rank's; a difference is
+ * DCC_EIO) and, when a rank fails, ends the others' exchanges instead of
+ * leaving them waiting.  Stats are the whole batch's on every rank, n_shards
+ * the ranks that took part, device_ms of a dcc_init_multi context the maximum
+ * over its ranks.  On a context without a communicator (or with one rank and
+ * no DCC_OPT_COMM_SOLO) the flag is ignored.  Out of scope: the lock-table
+ * handle (dcc_locktab_lock_epoch behaves as described there whatever the
+ * flag says), exchanging in list order instead of n_txn bytes per round, and
+ * pipelining sharded epochs; TIMESTAMP, MVCC, WAIT_DIE and MaaT are not
+ * key-sharded.
  * Stats: n_commit, n_abort, nnz_w (EX requests), n_readonly (txns with no EX
  * request), rounds, device_ms, total_ms, alg_bytes (dcc_nowait_alg_bytes);
  * with profiling phase_ms: 0 = table build, 1 = round 1, 2 = rounds >= 2,
@@ -840,7 +866,9 @@ uint64_t dcc_waitdie_carry_alg_bytes(uint64_t n_txn, uint64_t n_kept, uint64_t n
  * device memory; compact batch forms are accepted.  The table is created with
  * its capacity, lives on the context's GPU (rank 0's of a dcc_init_multi
  * context) and is freed by dcc_destroy if still alive.  A lock epoch under a
- * communicator of more than one rank is DCC_ENOTSUP.  No call is a
+ * communicator of more than one rank is DCC_ENOTSUP, with or without
+ * DCC_SHARD_SELF: the flag's key-sharded path is dcc_nowait_lock_epoch's
+ * alone, and dcc_locktab_lock_epoch ignores it.  No call is a
  * collective.  Pipelined OCC epochs in flight complete first.  Both table
  * buffers, the control words and the staging of host exports are allocated
  * at create, the per-epoch workspaces by dcc_reserve: a warmed-up call on a

@@ -5,14 +5,22 @@ batches: the C2 shape (65,536 x 16, theta 0.9) and the headline shape
 (1,048,576 x 16, theta 0.9).
 
     python tools/nowait_bench.py [--warmup 5] [--steps 20] [--shape both|c2|headline]
-                                 [--check-1m] [--json PATH]
+                                 [--check-1m] [--json PATH] [--shards R]
 
 device_ms is the engine's own device time of the decision (HIP events on its
 stream around the kernels of one call, batch resident); the table reports the
 median of the timed calls with the minimum and maximum, the rounds, and
 alg_bytes / device_ms.  Parity with the Row_lock replay (tests/nowait_ref.py)
 is checked on the C2 shape after timing; --check-1m also replays the headline
-shape (~30 s of Python).  Phase times come from a separate profiled call."""
+shape (~30 s of Python).  Phase times come from a separate profiled call.
+
+--shards R times the key-sharded epoch (DCC_SHARD_SELF) alone,
+on Engine(devices=[0] * R): R ranks that share cuda:0 and exchange through the
+host, so the figures show what sharding costs and how much smaller a rank's
+lock table is, not how it scales.  R = 1 is the unflagged epoch on one
+context.  device_ms is the maximum over the ranks; the collectives come from
+dcc_comm_calls, the table bytes from the sizing rule (16-byte slots, the next
+power of two above 1.25 x the rank's own requests, at least 1,024)."""
 import argparse
 import json
 import os
@@ -40,6 +48,58 @@ def summary(stats):
             "n_commit": stats[-1]["n_commit"], "n_abort": stats[-1]["n_abort"]}
 
 
+def table_bytes(requests):
+    cap = 1024
+    while cap < requests + requests // 4 + 1:
+        cap *= 2
+    return 16 * cap
+
+
+def run_shards(a):
+    R = a.shards
+    out = {}
+    with (d.Engine(0) if R == 1 else d.Engine(devices=[0] * R)) as eng:
+        for name, n in (("C2 65,536 x 16", 65536), ("headline 1,048,576 x 16", 1 << 20)):
+            if a.shape != "both" and (a.shape == "c2") != (n == 65536):
+                continue
+            b = d.gen_ycsb(n_txn=n, zipf_theta=0.9)
+            db = b.to_torch("cuda:0")
+            rc = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+            cf = torch.empty(n, dtype=torch.int32, device="cuda:0")
+            eng.reserve(b.n_txn, b.nnz)
+
+            def nowait():
+                return eng.nowait_lock_epoch(db, out_rc=rc, out_conflict=cf, shard=R > 1)[2]
+
+            for _ in range(a.warmup):
+                nowait()
+            c0 = eng.comm_calls
+            st = [nowait() for _ in range(a.steps)]
+            torch.cuda.synchronize()
+            res = summary(st)
+            assert st[-1]["n_shards"] == R
+            res["shards"] = R
+            res["collectives_per_epoch"] = (eng.comm_calls - c0) / (R * a.steps)
+            res["bytes_exchanged_per_rank"] = int(res["collectives_per_epoch"] * n)
+            own = np.bincount(d.shard_of_keys(np.asarray(b.keys), R), minlength=R)
+            res["own_requests"] = own.tolist()
+            res["table_bytes_per_rank"] = [table_bytes(int(c)) for c in own]
+            res["table_bytes_one_gpu"] = table_bytes(b.nnz)
+            if n == 65536 or a.check_1m:
+                erc, ecf = replay(b)
+                res["parity_vs_replay"] = bool(
+                    np.array_equal(rc.cpu().numpy(), erc)
+                    and np.array_equal(cf.cpu().numpy().view(np.uint32), ecf))
+            out[name] = res
+            print(f"{name}: shards {R}  device_ms {res['device_ms']:.3f} (min {res['device_ms_min']:.3f}, "
+                  f"max {res['device_ms_max']:.3f})  rounds {res['rounds']}  "
+                  f"collectives {res['collectives_per_epoch']:.1f}  "
+                  f"exchanged {res['bytes_exchanged_per_rank']} B  "
+                  f"table {max(res['table_bytes_per_rank'])} B of {res['table_bytes_one_gpu']} B"
+                  + (f"  parity_vs_replay {res['parity_vs_replay']}" if "parity_vs_replay" in res else ""))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -48,12 +108,16 @@ def main():
                     help="one shape only (for a kernel trace of that shape)")
     ap.add_argument("--check-1m", action="store_true")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--shards", type=int, default=0,
+                    help="time the key-sharded epoch on R ranks sharing cuda:0 (1: the unflagged epoch)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "nowait_bench needs cuda:0"
     out = {}
+    if a.shards:
+        out = run_shards(a)
     with d.Engine(0) as eng:
         for name, n in (("C2 65,536 x 16", 65536), ("headline 1,048,576 x 16", 1 << 20)):
-            if a.shape != "both" and (a.shape == "c2") != (n == 65536):
+            if a.shards or (a.shape != "both" and (a.shape == "c2") != (n == 65536)):
                 continue
             b = d.gen_ycsb(n_txn=n, zipf_theta=0.9)
             db = b.to_torch("cuda:0")
