@@ -37,6 +37,9 @@ KEYS_U32 = 0x10
 ACCTYPE_2BIT = 0x20
 TN_U32 = 0x40
 SHARD_SELF = 0x80
+ISO_SERIALIZABLE = 0
+ISO_READ_COMMITTED = 0x100
+ISO_READ_UNCOMMITTED = 0x200
 MAAT_READ_AND_PREWRITE = 0x4
 ROW_NONE = 0xFFFFFFFFFFFFFFFF
 UNIQUE_ID_BYTES = 128
@@ -291,6 +294,7 @@ _SIGS = [
     ("dcc_nowait_lock_epoch", C.c_int,
      [_P, C.POINTER(Batch), C.POINTER(CalvinHeld), _P, _P, C.POINTER(Stats)]),
     ("dcc_nowait_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
+    ("dcc_nowait_iso_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32]),
     ("dcc_tso_validate_epoch", C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, C.POINTER(Stats)]),
     ("dcc_tso_rows_set", C.c_int, [_P, _P, _P, _P, C.c_uint64]),
     ("dcc_tso_rows_get", C.c_int, [_P, _P, _P, _P, C.c_uint64]),

@@ -211,6 +211,8 @@ struct LtEpoch {
   uint32_t lp = 0;                 // log2 lanes per txn
   const uint32_t* err = nullptr;   // the epoch's error word
   unsigned grid = 1;
+  uint32_t mask = 0;   // the per-epoch table's
+  uint32_t level = 0;  // 0 SERIALIZABLE, 1 READ_COMMITTED, 2 READ_UNCOMMITTED
 };
 
 struct dcc_ctx {

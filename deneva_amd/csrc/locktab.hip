@@ -29,6 +29,16 @@
 //                between threads is needed.
 // Both use the P-lanes-per-txn layout of the k_nw_* kernels (nowait_lanes.h).
 //
+// Isolation levels (DCC_ISO_*).  READ_COMMITTED: a read may
+// meet a row that is EX-held in this table alone.  Of the two ways to tell it
+// so, the reads keep a per-epoch slot whenever a table handle is present
+// (k_nw_build_rd inserts instead of looking up; they still publish nothing),
+// and k_lt_seed stays as it is.  k_lt_grant<true> keeps the EX requests of the
+// committed txns only.  READ_UNCOMMITTED: k_lt_seed<true> enters the held rows
+// the epoch requests into the per-epoch table itself (there is no build), and
+// nothing is granted.  The release kernels take the accesses of the level:
+// all of them, the EX ones, or none (REL_*).
+//
 // A release is four launches back to back and one host synchronisation:
 //   k_lt_rcheck  the offsets, before anything indexes with them
 //   k_lt_radd    per selected access: find the row (not found: verdict), keep
@@ -164,8 +174,12 @@ struct LtSeed {
   uint32_t lp;
   const LtSlot* lt;
   uint32_t mask;
+  uint32_t emask;  // INS: the per-epoch table's mask
+  uint32_t* err;   // INS: the epoch's error word
 };
 
+// INS (READ_UNCOMMITTED): no request has a per-epoch slot; a held row gets one here.
+template <bool INS>
 __global__ __launch_bounds__(NW_T) void k_lt_seed(LtSeed A) {
   const Seg g = seg_of(A.lp);
   const uint32_t gpb = NW_T >> A.lp;
@@ -175,12 +189,23 @@ __global__ __launch_bounds__(NW_T) void k_lt_seed(LtSeed A) {
     const uint32_t o0 = A.off[t], len = A.off[t + 1] - o0;
     if (g.a >= len) continue;
     const uint64_t x = (uint64_t)o0 + g.a;
-    const uint32_t s = A.sid[x];
-    if (s == SID_NONE) continue;  // the epoch fails on its own (per-epoch table full)
+    uint32_t s = SID_NONE;
+    if constexpr (!INS) {
+      s = A.sid[x];
+      if (s == SID_NONE) continue;  // the epoch fails on its own (per-epoch table full)
+    }
     const uint32_t h = lt_find(A.lt, A.mask, A.keys[x]);
     if (h == SID_NONE) continue;
     const uint32_t w = A.lt[h].word;
     if ((w & LT_CNT) == 0) continue;
+    if constexpr (INS) {
+      bool claimed;
+      s = probe_insert<ProbeDouble>(A.tab, A.emask, A.keys[x], claimed);
+      if (s == SID_NONE) {
+        atomicOr(A.err, NW_ERR_FULL);
+        continue;
+      }
+    }
     own_min(&A.tab[s].own, 0u);  // a held row: the committed word below every txn
     if (w & LT_EX) own_min(&A.tab[s].aux, 0u);
   }
@@ -202,6 +227,8 @@ struct LtGrant {
   uint32_t* ctl;
 };
 
+// EXONLY (READ_COMMITTED): the read locks were released right after the reads.
+template <bool EXONLY>
 __global__ __launch_bounds__(NW_T) void k_lt_grant(LtGrant A) {
   __shared__ LtComb C;
   __shared__ uint32_t s_new, s_rows, s_holds, s_err, s_stop;
@@ -232,6 +259,7 @@ __global__ __launch_bounds__(NW_T) void k_lt_grant(LtGrant A) {
       v = g.a < len;
       x = (uint64_t)o0 + g.a;
     }
+    if constexpr (EXONLY) v = v && is_ex(A.at[x]);
     if (v) {
       bool claimed;
       const uint32_t h = lt_insert(A.lt, A.mask, A.keys[x], claimed);
@@ -287,7 +315,10 @@ struct LtRel {
   uint32_t mask;
   uint32_t* sid;  // [nnz] the row's slot of every selected access
   uint32_t* ctl;
+  const uint8_t* at;  // REL_EX: the access types
 };
+// the accesses of a selected txn that are released: SERIALIZABLE, READ_COMMITTED, READ_UNCOMMITTED
+constexpr int REL_ALL = 0, REL_EX = 1, REL_NONE = 2;
 
 __global__ __launch_bounds__(NW_T) void k_lt_rcheck(const uint32_t* __restrict__ off, uint64_t n, uint64_t nnz,
                                                     uint32_t* __restrict__ ctl) {
@@ -303,8 +334,8 @@ __global__ __launch_bounds__(NW_T) void k_lt_rcheck(const uint32_t* __restrict__
 // The selected accesses of the lanes' txns, one after the other: f(x) with x
 // the access' position in keys / sid; step_end() by every thread after each
 // step of the workgroup.  Returns through sel_n / sel_m what the txns' first
-// lanes counted.
-template <class F, class G>
+// lanes counted (REL_EX: every lane, its own released accesses).
+template <int REL, class F, class G>
 __device__ inline void rel_for_each(const LtRel& A, uint32_t& sel_n, uint32_t& sel_m, F f, G step_end) {
   const uint32_t P = 1u << A.lp, a = threadIdx.x & (P - 1), gl = threadIdx.x >> A.lp;
   const uint32_t gpb = NW_T >> A.lp;
@@ -319,14 +350,23 @@ __device__ inline void rel_for_each(const LtRel& A, uint32_t& sel_n, uint32_t& s
       }
       if (a == 0) {
         sel_n++;
-        sel_m += len;
+        if constexpr (REL == REL_ALL) sel_m += len;
       }
-      for (uint32_t q = a; q < len; q += P) f(o0 + q);
+      if constexpr (REL == REL_ALL) {
+        for (uint32_t q = a; q < len; q += P) f(o0 + q);
+      } else if constexpr (REL == REL_EX) {
+        for (uint32_t q = a; q < len; q += P)
+          if (is_ex(A.at[o0 + q])) {
+            sel_m++;
+            f(o0 + q);
+          }
+      }
     }
     step_end();
   }
 }
 
+template <int REL>
 __global__ __launch_bounds__(NW_T) void k_lt_radd(LtRel A) {
   __shared__ LtComb C;
   __shared__ uint32_t s_n, s_m, s_err;
@@ -340,7 +380,7 @@ __global__ __launch_bounds__(NW_T) void k_lt_radd(LtRel A) {
   __syncthreads();
   uint32_t sel_n = 0, sel_m = 0, err = 0, step = 0;
   auto add = [&](uint32_t h, uint32_t c) { atomicAdd(&A.lt[h].rel, c); };
-  rel_for_each(
+  rel_for_each<REL>(
       A, sel_n, sel_m,
       [&](uint64_t x) {
         const uint32_t h = lt_find(A.lt, A.mask, A.keys[x]);
@@ -363,11 +403,12 @@ __global__ __launch_bounds__(NW_T) void k_lt_radd(LtRel A) {
   }
 }
 
+template <int REL>
 __global__ __launch_bounds__(NW_T) void k_lt_rcmp(LtRel A) {
   if (A.ctl[LT_C_ERR] & (LT_ERR_OFF | LT_ERR_MISS)) return;  // set by the launches before only
   uint32_t sel_n = 0, sel_m = 0;
   bool over = false;
-  rel_for_each(
+  rel_for_each<REL>(
       A, sel_n, sel_m,
       [&](uint64_t x) {
         const LtSlot* s = &A.lt[A.sid[x]];
@@ -377,6 +418,7 @@ __global__ __launch_bounds__(NW_T) void k_lt_rcmp(LtRel A) {
   if (over) atomicOr(&A.ctl[LT_C_ERR], LT_ERR_OVER);
 }
 
+template <int REL>
 __global__ __launch_bounds__(NW_T) void k_lt_rapply(LtRel A) {
   __shared__ LtComb C;
   __shared__ uint32_t s_freed;
@@ -396,7 +438,7 @@ __global__ __launch_bounds__(NW_T) void k_lt_rapply(LtRel A) {
     }
     A.lt[h].rel = 0;  // whoever touches the row stores the same zero
   };
-  rel_for_each(
+  rel_for_each<REL>(
       A, sel_n, sel_m,
       [&](uint64_t x) {
         const uint32_t h = A.sid[x];
@@ -496,8 +538,10 @@ int dcc_ctx::locktab_begin(dcc_locktab* lt, uint64_t incoming, const char* what)
 int dcc_ctx::locktab_seed(dcc_locktab* lt, const LtEpoch& E) {
   dcc_ctx* ctx = this;
   if (profiling) CK(hipEventRecord(pev[5], stream));
-  LtSeed A{E.n, E.off, E.keys, E.sid, E.tab, E.lp, (const LtSlot*)lt->tab[lt->cur].p, (uint32_t)(lt->n_slots - 1)};
-  k_lt_seed<<<E.grid, NW_T, 0, stream>>>(A);
+  LtSeed A{E.n,    E.off, E.keys, E.sid, E.tab, E.lp, (const LtSlot*)lt->tab[lt->cur].p, (uint32_t)(lt->n_slots - 1),
+           E.mask, (uint32_t*)E.err};
+  if (E.level == 2) k_lt_seed<true><<<E.grid, NW_T, 0, stream>>>(A);
+  else k_lt_seed<false><<<E.grid, NW_T, 0, stream>>>(A);
   CK(hipGetLastError());
   return DCC_OK;
 }
@@ -509,7 +553,9 @@ int dcc_ctx::locktab_grant(dcc_locktab* lt, const LtEpoch& E) {
   LtGrant A{E.n, E.off, E.keys, E.at, E.state, E.lp, E.err, (LtSlot*)lt->tab[lt->cur].p, (uint32_t)(lt->n_slots - 1),
             ctl};
   // fewer, longer workgroups than the epoch's passes: the combiner folds what one workgroup sees
-  k_lt_grant<<<launch_grid(E.n, NW_T >> E.lp, (unsigned)n_cu * 4), NW_T, 0, stream>>>(A);
+  const unsigned grid = launch_grid(E.n, NW_T >> E.lp, (unsigned)n_cu * 4);
+  if (E.level == 1) k_lt_grant<true><<<grid, NW_T, 0, stream>>>(A);
+  else if (E.level == 0) k_lt_grant<false><<<grid, NW_T, 0, stream>>>(A);  // READ_UNCOMMITTED: nothing stays
   CK(hipGetLastError());
   CK(hipMemcpyAsync((uint8_t*)hmisc + LT_HMISC_OFF, ctl, LT_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
   return DCC_OK;
@@ -579,8 +625,13 @@ int dcc_ctx::locktab_release(dcc_locktab* lt, const dcc_batch* b, const uint8_t*
   if (out_n) *out_n = 0;
   if (out_nnz) *out_nnz = 0;
   LtRel A{};
+  int rel = REL_ALL;
   if (b) {
     CR(check_batch(b, false));  // txn length is free here; the offsets are checked on the device
+    const uint32_t iso = b->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED);
+    if (iso == (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
+      return fail(DCC_EINVAL, "lock table release: both isolation bits set");
+    rel = iso == DCC_ISO_READ_COMMITTED ? REL_EX : iso ? REL_NONE : REL_ALL;
     A.n = b->n_txn;
   } else {
     if (n_keys && !keys) return fail(DCC_EINVAL, "lock table release: null keys");
@@ -600,6 +651,7 @@ int dcc_ctx::locktab_release(dcc_locktab* lt, const dcc_batch* b, const uint8_t*
     A.nnz = d.nnz;
     A.off = d.off;
     A.keys = d.keys;
+    A.at = d.acctype;
     A.S.want = want;
     if (rc_in) CR(stage(lt->st_rc, rc_in, A.n, dev, "lock table release rc", A.S.rc));
     // lanes per txn: the power of two at or above the mean length, 64 at most
@@ -624,11 +676,15 @@ int dcc_ctx::locktab_release(dcc_locktab* lt, const dcc_batch* b, const uint8_t*
   if (prof) CK(hipEventRecord(pev[0], stream));
   if (A.off) k_lt_rcheck<<<launch_grid(A.n, NW_T * 4, max_grid), NW_T, 0, stream>>>(A.off, A.n, A.nnz, ctl);
   if (prof) CK(hipEventRecord(pev[1], stream));
-  k_lt_radd<<<grid_c, NW_T, 0, stream>>>(A);
+  if (rel == REL_EX) k_lt_radd<REL_EX><<<grid_c, NW_T, 0, stream>>>(A);
+  else if (rel == REL_NONE) k_lt_radd<REL_NONE><<<grid_c, NW_T, 0, stream>>>(A);  // counts the selected txns
+  else k_lt_radd<REL_ALL><<<grid_c, NW_T, 0, stream>>>(A);
   if (prof) CK(hipEventRecord(pev[2], stream));
-  k_lt_rcmp<<<grid, NW_T, 0, stream>>>(A);
+  if (rel == REL_EX) k_lt_rcmp<REL_EX><<<grid, NW_T, 0, stream>>>(A);
+  else if (rel == REL_ALL) k_lt_rcmp<REL_ALL><<<grid, NW_T, 0, stream>>>(A);
   if (prof) CK(hipEventRecord(pev[3], stream));
-  k_lt_rapply<<<grid_c, NW_T, 0, stream>>>(A);
+  if (rel == REL_EX) k_lt_rapply<REL_EX><<<grid_c, NW_T, 0, stream>>>(A);
+  else if (rel == REL_ALL) k_lt_rapply<REL_ALL><<<grid_c, NW_T, 0, stream>>>(A);
   CK(hipGetLastError());
   if (prof) CK(hipEventRecord(pev[4], stream));
   CK(hipEventRecord(ev1, stream));

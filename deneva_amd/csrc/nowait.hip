@@ -56,6 +56,24 @@
 // its readers for that one round and carry a stale tag from round 2 on.
 // After the fixed point each rank's first conflicting request goes through
 // one more byte-MAX exchange as 64 - ordinal (k_nw_final, k_nw_conf).
+//
+// Isolation levels (DCC_ISO_*): the same replay with the
+// reference's early releases.  READ_COMMITTED releases a read lock right after
+// the read, so a read leaves nothing: only EX requests get a slot and a word.
+// `aux` is the minimum EX requester, `own` only says "held in any mode" (the
+// tag-0 word 0); an EX access reads both, an SH access `aux`.  The build is
+// two launches, for the grid-wide order between them:
+//           k_nw_build_ex  EX requests: table_insert, sid[], round-1 `aux` word
+//           k_nw_build_rd  RD/SCAN requests: table_find (SID_ABSENT: the row is
+//                          not in the table, the request can never conflict);
+//                          self-conflicts (an earlier access of the slot is EX)
+// The round-1 words are out before k_nw_build_rd knows the self-conflicts: the
+// words of a self-aborted txn cost its readers one blocked round, exactly as
+// the key-sharded path's above, and carry a stale tag from round 2 on.
+// The rounds are the ISO instantiations of k_nw_decide / k_nw_publish /
+// k_nw_final.  READ_UNCOMMITTED releases every lock after its access: no
+// access leaves a trace, k_nw_ru decides every txn against the held rows in
+// one pass, and without held rows no table is built.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -77,21 +95,31 @@ namespace {
 
 constexpr uint32_t NW_STAGE = 1024;   // blocked txns a workgroup stages before one list append
 // error bits next to CHK_ERR_* (a held key sets CHK_ERR_KEY too)
-constexpr uint32_t NW_ERR_FULL = 4, NW_ERR_STATE = 8;
+constexpr uint32_t NW_ERR_STATE = 8;  // NW_ERR_FULL = 4: nowait_lanes.h
 // counter words (nw_misc) next to SEG_C_ERR / SEG_C_MAXLEN; the ring holds the list lengths
 constexpr uint32_t NW_C_NEX = 2, NW_C_RO = 3, NW_C_COMMIT = 4, NW_C_RING = 8, NW_C_WORDS = NW_C_RING + SEG_RING;
 // key-sharded: the rank's own requests / held rows, the reserved key in the held list
 constexpr uint32_t NW_C_OWN = 5, NW_C_OWNHELD = 6, NW_ERR_HKEY = 16;
 // sid[] of a request whose row another rank owns (SID_NONE: table full)
 constexpr uint32_t SID_REMOTE = SID_NONE - 1;
+// sid[] of a READ_COMMITTED read whose row is not in the table: nobody holds or
+// writes it.  The levels never run key-sharded, so no kernel sees both.
+constexpr uint32_t SID_ABSENT = SID_NONE - 2;
+// the EX requests of the batch, counted next to the batch check
+constexpr uint32_t NW_C_EXREQ = 7;
+// the level of an epoch (a template parameter of the rounds' kernels)
+constexpr int ISO_SER = 0, ISO_RC = 1;
 // status bytes of a sharded round
 constexpr uint8_t NW_S_BLOCKED = 1, NW_S_KILLED = 2;
 
-// the request has a slot in this rank's table
-template <bool SH>
+// the request has a slot in this rank's table; READ_COMMITTED (never key-sharded):
+// its row is held or has an EX request
+template <bool SH, int ISO = ISO_SER>
 __device__ inline bool has_slot(uint32_t s) {
+  if constexpr (ISO == ISO_RC) return s < SID_ABSENT;
   return SH ? s < SID_REMOTE : s != SID_NONE;
 }
+__device__ inline bool rc_slot(uint32_t s) { return has_slot<false, ISO_RC>(s); }
 
 // A txn names a row twice with EX on either side (NO_WAIT keeps no owner
 // list, row_lock.cpp:176-182): the lanes of the later requests.  Rows compare
@@ -105,6 +133,21 @@ __device__ inline bool self_conflict(const Seg& g, uint32_t lp, bool v, uint32_t
     const uint32_t so = __shfl(s, (int)(g.seg0 + q));
     const uint32_t eo = __shfl(ex, (int)(g.seg0 + q));
     if (v && q < g.a && so == s && has_slot<SH>(s) && (ex | eo)) sc = true;
+  }
+  return sc;
+}
+
+// READ_COMMITTED: only an earlier EX of the txn is still there (its reads are
+// released at once): RD then WR of a row is fine, WR then RD and WR then WR
+// abort at the second.  Every lane of the wave calls it.
+__device__ inline bool self_conflict_rc(const Seg& g, uint32_t lp, bool v, uint32_t s, uint32_t ex) {
+  bool sc = false;
+  const uint32_t P = 1u << lp;
+  for (uint32_t q = 0; q + 1 < P; q++) {
+    if (!ballot64(v && g.a > q)) break;  // no lane of the wave has an earlier access q
+    const uint32_t so = __shfl(s, (int)(g.seg0 + q));
+    const uint32_t eo = __shfl(ex, (int)(g.seg0 + q));
+    if (v && q < g.a && so == s && rc_slot(s) && eo) sc = true;
   }
   return sc;
 }
@@ -145,6 +188,18 @@ __global__ __launch_bounds__(CHK_T) void k_nw_count(const uint64_t* __restrict__
     if (own) atomicAdd(&cnt[NW_C_OWN], own);
     if (ownh) atomicAdd(&cnt[NW_C_OWNHELD], ownh);
   }
+}
+
+// READ_COMMITTED: the EX requests of the batch, the table's size next to the
+// held rows.  Every index is below nnz: it runs next to the batch check.
+__global__ __launch_bounds__(CHK_T) void k_nw_count_ex(const uint8_t* __restrict__ at, uint64_t nnz,
+                                                       uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t s_a[CHK_T / 64];
+  const uint64_t tid = (uint64_t)blockIdx.x * CHK_T + threadIdx.x, stride = (uint64_t)gridDim.x * CHK_T;
+  uint32_t nex = 0;
+  for (uint64_t x = tid; x < nnz; x += stride) nex += is_ex(at[x]);
+  nex = block_reduce<CHK_T / 64, AddOp<uint32_t>>(nex, s_a);
+  if (threadIdx.x == 0 && nex) atomicAdd(&cnt[NW_C_EXREQ], nex);
 }
 
 template <bool SH>
@@ -247,6 +302,151 @@ __global__ __launch_bounds__(NW_T) void k_nw_build(NwA<SH> A) {
   }
 }
 
+// READ_COMMITTED build, first launch: the EX requests enter the table and
+// publish their round-1 word; a read takes nothing that outlives it.
+__global__ __launch_bounds__(NW_T) void k_nw_build_ex(NwArgs A) {
+  __shared__ uint32_t s_ro, s_nex;
+  if (threadIdx.x == 0) {
+    s_ro = 0;
+    s_nex = 0;
+  }
+  __syncthreads();
+  const Seg g = seg_of(A.lp);
+  const uint32_t gpb = NW_T >> A.lp;
+  uint32_t ro = 0, nex = 0;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
+    const uint64_t t = g0 + g.gl;
+    const bool tv = t < A.n;
+    uint32_t o0 = 0, len = 0;
+    if (tv) {
+      o0 = A.off[t];
+      len = A.off[t + 1] - o0;
+    }
+    const bool v = tv && g.a < len;
+    const uint64_t x = (uint64_t)o0 + g.a;
+    const bool ex = v && is_ex(A.at[x]);
+    if (ex) {
+      const uint32_t s = table_insert(A.tab, A.mask, A.keys[x]);
+      A.sid[x] = s;
+      if (s == SID_NONE) atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_FULL);
+      else own_min(&A.tab[s].aux, own_word(round_tag(1), (uint32_t)t + 1u));
+    }
+    const uint64_t exb = ballot64(ex) & g.mask;
+    if (tv && g.a == 0) {
+      A.state[t] = ST_UNDECIDED;
+      ro += exb ? 0u : 1u;
+      nex += (uint32_t)__popcll(exb);
+    }
+  }
+  if (ro) atomicAdd(&s_ro, ro);
+  if (nex) atomicAdd(&s_nex, nex);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_ro) atomicAdd(&A.cnt[NW_C_RO], s_ro);
+    if (s_nex) atomicAdd(&A.cnt[NW_C_NEX], s_nex);
+  }
+}
+
+// READ_COMMITTED build, second launch (every EX row is in the table): the
+// reads look their row up, SID_ABSENT for a row nobody holds or writes; with
+// `insert` (a lock table seeds the held rows through the requests' slots,
+// k_lt_seed) a read takes a slot too, and still publishes nothing.  Both slot
+// ids of a pair are known here, so this pass decides the self-conflicts; the
+// round-1 words of such a txn are out already and block its readers for that
+// one round (the header comment).
+__global__ __launch_bounds__(NW_T) void k_nw_build_rd(NwArgs A, bool insert) {
+  const Seg g = seg_of(A.lp);
+  const uint32_t gpb = NW_T >> A.lp;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
+    const uint64_t t = g0 + g.gl;
+    const bool tv = t < A.n;
+    uint32_t o0 = 0, len = 0;
+    if (tv) {
+      o0 = A.off[t];
+      len = A.off[t + 1] - o0;
+    }
+    const bool v = tv && g.a < len;
+    const uint64_t x = (uint64_t)o0 + g.a;
+    uint32_t ex = 0, s = SID_NONE;
+    if (v) {
+      ex = is_ex(A.at[x]);
+      if (ex) {
+        s = A.sid[x];
+      } else {
+        const uint64_t key = A.keys[x];
+        if (insert) {
+          s = table_insert(A.tab, A.mask, key);
+          if (s == SID_NONE) atomicOr(&A.cnt[SEG_C_ERR], NW_ERR_FULL);
+        } else {
+          s = table_find(A.tab, A.mask, key);
+          if (s == SID_NONE) s = SID_ABSENT;
+        }
+        A.sid[x] = s;
+      }
+    }
+    const bool sc = self_conflict_rc(g, A.lp, v, s, ex);
+    const bool selfc = (ballot64(sc) & g.mask) != 0;
+    if (tv && g.a == 0 && selfc) A.state[t] = ST_ABORT;
+  }
+}
+
+// READ_UNCOMMITTED: every lock is released right after its access, so no
+// access of the epoch leaves a trace and a txn meets the held rows alone:
+// killed iff a row of its is EX-held (`aux` == 0), or held in any mode (`own`
+// == 0) and the access EX.  One pass: state, RC, the first such ordinal, the
+// counts.  tab == nullptr: no held rows, everything commits.
+__global__ __launch_bounds__(NW_T) void k_nw_ru(NwArgs A, uint8_t* __restrict__ rc, uint32_t* __restrict__ conflict) {
+  __shared__ uint32_t s_ro, s_nex, s_commit;
+  if (threadIdx.x == 0) {
+    s_ro = 0;
+    s_nex = 0;
+    s_commit = 0;
+  }
+  __syncthreads();
+  const Seg g = seg_of(A.lp);
+  const uint32_t gpb = NW_T >> A.lp;
+  uint32_t ro = 0, nex = 0, commits = 0;
+  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
+    const uint64_t t = g0 + g.gl;
+    const bool tv = t < A.n;
+    uint32_t o0 = 0, len = 0;
+    if (tv) {
+      o0 = A.off[t];
+      len = A.off[t + 1] - o0;
+    }
+    const bool v = tv && g.a < len;
+    const uint64_t x = (uint64_t)o0 + g.a;
+    uint32_t ex = 0;
+    bool c = false;
+    if (v) {
+      ex = is_ex(A.at[x]);
+      if (A.tab) {
+        const uint32_t s = table_find(A.tab, A.mask, A.keys[x]);
+        if (s != SID_NONE) c = A.tab[s].aux == 0u || (ex && A.tab[s].own == 0u);
+      }
+    }
+    const uint64_t cb = ballot64(c) & g.mask;
+    const uint64_t exb = ballot64(v && ex) & g.mask;
+    if (tv && g.a == 0) {
+      A.state[t] = cb ? ST_ABORT : ST_COMMIT;
+      rc[t] = cb ? DCC_RC_ABORT : DCC_RC_RCOK;
+      if (conflict) conflict[t] = cb ? (uint32_t)__builtin_ctzll(cb) - g.seg0 : DCC_ACCESS_NONE;
+      commits += cb ? 0u : 1u;
+      ro += exb ? 0u : 1u;
+      nex += (uint32_t)__popcll(exb);
+    }
+  }
+  if (ro) atomicAdd(&s_ro, ro);
+  if (nex) atomicAdd(&s_nex, nex);
+  if (commits) atomicAdd(&s_commit, commits);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_ro) atomicAdd(&A.cnt[NW_C_RO], s_ro);
+    if (s_nex) atomicAdd(&A.cnt[NW_C_NEX], s_nex);
+    if (s_commit) atomicAdd(&A.cnt[NW_C_COMMIT], s_commit);
+  }
+}
+
 // One round.  list == nullptr: every txn (round 1), else the *m_in txns of
 // the list.  Blocked txns are staged in LDS and appended to list_out with one
 // atomic per NW_STAGE of them (the list order is free: decisions do not
@@ -256,8 +456,9 @@ __global__ __launch_bounds__(NW_T) void k_nw_build(NwA<SH> A) {
 // the status byte of every txn it finds blocked or killed on this rank's rows
 // (the bytes are clear before it; a txn the build marked is left alone),
 // NW_APPLY takes the reduced byte in place of the ballots and clears it.
+// ISO_RC (not key-sharded): the words of READ_COMMITTED, see the header comment.
 constexpr int NW_ONE = 0, NW_EVAL = 1, NW_APPLY = 2;
-template <int MODE>
+template <int MODE, int ISO = ISO_SER>
 __global__ __launch_bounds__(NW_T) void k_nw_decide(NwA<MODE != NW_ONE> A, uint32_t tag,
                                                     const uint32_t* __restrict__ list,
                                                     const uint32_t* __restrict__ m_in,
@@ -311,7 +512,14 @@ __global__ __launch_bounds__(NW_T) void k_nw_decide(NwA<MODE != NW_ONE> A, uint3
       if (v) {
         ex = is_ex(A.at[x]);
         s = A.sid[x];
-        if (has_slot<SH>(s)) ps = own_status(ex ? A.tab[s].own : A.tab[s].aux, tag, t + 1u);
+        if constexpr (ISO == ISO_RC) {
+          if (rc_slot(s)) {
+            ps = own_status(A.tab[s].aux, tag, t + 1u);
+            if (ex && A.tab[s].own == 0u) ps |= PS_KILLED;  // held in any mode
+          }
+        } else {
+          if (has_slot<SH>(s)) ps = own_status(ex ? A.tab[s].own : A.tab[s].aux, tag, t + 1u);
+        }
       }
       killed = (ballot64(ps & PS_KILLED) & g.mask) != 0;
       blocked = !killed && (ballot64(ps & PS_BLOCKED) & g.mask) != 0;
@@ -320,7 +528,9 @@ __global__ __launch_bounds__(NW_T) void k_nw_decide(NwA<MODE != NW_ONE> A, uint3
       if (act && g.a == 0 && (killed || blocked)) A.stat[t] = killed ? NW_S_KILLED : NW_S_BLOCKED;
       continue;
     }
-    if (v && !killed && !blocked && has_slot<SH>(s)) {  // commit: hold every lock to the end of the epoch
+    if constexpr (ISO == ISO_RC) {  // commit: the EX locks stay to the end of the epoch
+      if (v && !killed && !blocked && ex && rc_slot(s)) own_min(&A.tab[s].aux, t + 1u);
+    } else if (v && !killed && !blocked && has_slot<SH>(s)) {  // commit: hold every lock to the end of the epoch
       own_min(&A.tab[s].own, t + 1u);
       if (ex) own_min(&A.tab[s].aux, t + 1u);
     }
@@ -344,7 +554,7 @@ __global__ __launch_bounds__(NW_T) void k_nw_decide(NwA<MODE != NW_ONE> A, uint3
 
 // The words of round `tag` for the txns still undecided (the list of the
 // round before).  Workgroup 0 clears the length word that round appends to.
-template <bool SH>
+template <bool SH, int ISO = ISO_SER>
 __global__ __launch_bounds__(NW_T) void k_nw_publish(NwA<SH> A, uint32_t tag, const uint32_t* __restrict__ list,
                                                      const uint32_t* __restrict__ m_in, uint32_t* m_zero) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *m_zero = 0;
@@ -358,6 +568,12 @@ __global__ __launch_bounds__(NW_T) void k_nw_publish(NwA<SH> A, uint32_t tag, co
     const uint32_t o0 = A.off[t], len = A.off[t + 1] - o0;
     if (g.a >= len) continue;
     const uint64_t x = (uint64_t)o0 + g.a;
+    if constexpr (ISO == ISO_RC) {  // one word per EX request; a read publishes nothing
+      if (!is_ex(A.at[x])) continue;
+      const uint32_t s = A.sid[x];
+      if (rc_slot(s)) own_min(&A.tab[s].aux, own_word(tag, t + 1u));
+      continue;
+    }
     const uint32_t s = A.sid[x];
     if (!has_slot<SH>(s)) continue;
     const uint32_t w = own_word(tag, t + 1u);
@@ -383,7 +599,9 @@ __global__ __launch_bounds__(NW_T) void k_nw_retag(Slot* tab, uint64_t cap) {
 // ordinal in the whole txn (1 .. 64, MAX_TXN_LEN is 64; 0: none here) into the
 // status byte, whose byte-MAX over the ranks is the lowest ordinal
 // (k_nw_conf); `conflict` only says whether the ordinals are wanted.
-template <bool SH>
+// READ_COMMITTED: the first access that has an earlier EX of its own on its
+// slot, or a tag-0 `aux` word below the txn, or (when EX) a held row.
+template <bool SH, int ISO = ISO_SER>
 __global__ __launch_bounds__(NW_T) void k_nw_final(NwA<SH> A, uint8_t* __restrict__ rc,
                                                    uint32_t* __restrict__ conflict) {
   __shared__ uint32_t s_commit;
@@ -422,12 +640,18 @@ __global__ __launch_bounds__(NW_T) void k_nw_final(NwA<SH> A, uint8_t* __restric
     if (v) {
       ex = is_ex(A.at[x]);
       s = A.sid[x];
-      if (has_slot<SH>(s)) {
+      if constexpr (ISO == ISO_RC) {
+        if (rc_slot(s)) {
+          const uint32_t w = A.tab[s].aux;
+          c = ((w >> IDX_BITS) == 0 && (w & IDX_MASK) < (uint32_t)t + 1u) || (ex && A.tab[s].own == 0u);
+        }
+      } else if (has_slot<SH>(s)) {
         const uint32_t w = ex ? A.tab[s].own : A.tab[s].aux;
         c = (w >> IDX_BITS) == 0 && (w & IDX_MASK) < (uint32_t)t + 1u;
       }
     }
-    c = self_conflict<SH>(g, A.lp, v, s, ex) || c;
+    if constexpr (ISO == ISO_RC) c = self_conflict_rc(g, A.lp, v, s, ex) || c;
+    else c = self_conflict<SH>(g, A.lp, v, s, ex) || c;
     const uint64_t cb = ballot64(c) & g.mask;
     if (tv && g.a == 0) {
       if constexpr (SH) {
@@ -485,6 +709,12 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   const bool sh = !lt && sharded() && (b->flags & DCC_SHARD_SELF) != 0;
   if (comm_ranks() > 1 && !sh)
     return fail(DCC_ENOTSUP, "nowait: more than one rank takes the whole epoch with DCC_SHARD_SELF and no lock table");
+  const uint32_t iso = b->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED);
+  if (iso == (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
+    return fail(DCC_EINVAL, "nowait: both isolation bits set");
+  const bool rcl = iso == DCC_ISO_READ_COMMITTED, rul = iso == DCC_ISO_READ_UNCOMMITTED;
+  if (sh && iso)  // on every rank alike, before any collective
+    return fail(DCC_ENOTSUP, "nowait: a key-sharded epoch is SERIALIZABLE only");
   if (sh) S.n_shards = (uint32_t)comm_ranks();
   const uint64_t hn = held ? held->n : 0;
   if (lt && hn) return fail(DCC_EINVAL, "nowait: a held list next to a lock table");
@@ -500,10 +730,14 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   CR(stage_batch(b, d));
   const uint64_t n = d.n, m = d.nnz;
   // key-sharded: the rank's own requests and held rows size the table, once they are counted below
-  uint64_t cap = sh ? 0 : table_capacity(m + hn);
+  // READ_COMMITTED: the held rows and the EX requests, once they are counted; with a lock table every
+  // request keeps a slot (k_lt_seed marks the held rows through them).  READ_UNCOMMITTED: the held rows
+  // alone, no table without them; of a lock table's rows at most one per request.
+  const bool late = sh || (rcl && !lt);
+  uint64_t cap = late ? 0 : rul ? (lt ? table_capacity(m) : hn ? table_capacity(hn) : 0) : table_capacity(m + hn);
   if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
-  CR(nowait_reserve(n, m, out_conflict != nullptr && !dev, !sh));
-  if (!sh) CR(table.ensure(this, cap * sizeof(Slot), "table"));
+  CR(nowait_reserve(n, m, out_conflict != nullptr && !dev, !sh && !iso));
+  if (!late && cap) CR(table.ensure(this, cap * sizeof(Slot), "table"));
   uint32_t* cnt = (uint32_t*)nw_misc.p;
   uint32_t* ring = cnt + NW_C_RING;
   uint32_t* lists[2] = {(uint32_t*)nw_list.p, (uint32_t*)nw_list.p + n};
@@ -523,8 +757,9 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
       d.off, n, d.keys, m, cnt);
   if (sh)
     k_nw_count<<<launch_grid(std::max(m, hn), CHK_T * 4, max_grid), CHK_T, 0, stream>>>(d.keys, m, hk, hn, who, cnt);
+  if (rcl) k_nw_count_ex<<<launch_grid(m, CHK_T * 4, max_grid), CHK_T, 0, stream>>>(d.acctype, m, cnt);
   CK(hipGetLastError());
-  CK(hipMemcpyAsync(hmisc, cnt, sh ? NW_C_RING * 4 : 8, hipMemcpyDeviceToHost, stream));
+  CK(hipMemcpyAsync(hmisc, cnt, sh || rcl ? NW_C_RING * 4 : 8, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   BatchShape shape;
   CR(batch_checked(this, (const uint32_t*)hmisc, m, false, shape));
@@ -535,6 +770,12 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
     if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
     CR(table.ensure(this, cap * sizeof(Slot), "table"));
   }
+  const uint64_t nnz_ex = rcl ? ((const uint32_t*)hmisc)[NW_C_EXREQ] : 0;
+  if (rcl && !lt) {
+    cap = table_capacity(nnz_ex + hn);
+    if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
+    CR(table.ensure(this, cap * sizeof(Slot), "table"));
+  }
   const uint32_t mask = (uint32_t)(cap - 1);
   const uint32_t lp = shape.lp;
   const uint64_t per_block = NW_T >> lp;  // txns per workgroup step
@@ -542,9 +783,10 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   const bool prof = profiling;
   CK(hipEventRecord(ev0, stream));
   if (prof) CK(hipEventRecord(pev[0], stream));
-  if (lt) CR(locktab_begin(lt, m, "lock epoch"));  // room for every request, or DCC_ERANGE
-  Slot* tab = (Slot*)table.p;
-  CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
+  // room for every request that can stay, or DCC_ERANGE
+  if (lt) CR(locktab_begin(lt, rcl ? nnz_ex : rul ? 0 : m, "lock epoch"));
+  Slot* tab = cap ? (Slot*)table.p : nullptr;
+  if (cap) CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
   if (hn) {
     if (sh) {
       k_nw_held<true><<<launch_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt, who);
@@ -558,6 +800,10 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   if (sh) {
     CK(hipMemsetAsync(AS.stat, 0, n, stream));  // every pass that sets a byte clears it again
     k_nw_build<true><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(AS);
+  } else if (rcl) {
+    k_nw_build_ex<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
+    k_nw_build_rd<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, lt != nullptr);
+  } else if (rul) {  // nothing to build: k_nw_ru looks the held rows up
   } else {
     k_nw_build<false><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
   }
@@ -575,6 +821,8 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
     L.lp = lp;
     L.err = &cnt[SEG_C_ERR];
     L.grid = launch_grid(n, per_block, max_grid);
+    L.mask = mask;
+    L.level = rcl ? 1 : rul ? 2 : 0;
     CR(locktab_seed(lt, L));
   }
   if (prof) CK(hipEventRecord(pev[1], stream));
@@ -609,6 +857,25 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
       CR(comm_allreduce_max_u8(AS.stat, n));
       k_nw_conf<<<launch_grid(n, NW_T * 4, max_grid), NW_T, 0, stream>>>(n, A.state, AS.stat, conf_dev, cnt);
     }
+  } else if (rul) {  // no rounds: one pass against the held rows
+    if (prof) CK(hipEventRecord(pev[2], stream));
+    k_nw_ru<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
+    if (prof) CK(hipEventRecord(pev[3], stream));
+  } else if (rcl) {  // one more round than SERIALIZABLE at most: the words of the self-aborted txns
+    CR(rounds_loop(this, ring, n, n + 3, "nowait", rounds,
+                   [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
+                     const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;
+                     const uint32_t tag = round_tag(er);
+                     const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
+                     const unsigned grid = launch_grid(bound, per_block, max_grid);
+                     if (r > 1) {
+                       if (er == 1) k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
+                       k_nw_publish<false, ISO_RC><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, left_out);
+                     }
+                     k_nw_decide<NW_ONE, ISO_RC>
+                         <<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
+                   }));
+    k_nw_final<false, ISO_RC><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
   } else {
     CR(rounds_loop(this, ring, n, n + 2, "nowait", rounds,
                    [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
@@ -644,7 +911,7 @@ int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8
   S.n_abort = n - hc[NW_C_COMMIT];
   S.nnz_w = hc[NW_C_NEX];
   S.n_readonly = hc[NW_C_RO];
-  S.alg_bytes = dcc_nowait_alg_bytes(n, m, out_conflict != nullptr);
+  S.alg_bytes = dcc_nowait_iso_alg_bytes(n, m, hn, out_conflict != nullptr, iso);
   if (lt) {
     uint64_t granted = 0;
     CR(locktab_end(lt, &granted));
@@ -661,12 +928,23 @@ extern "C" uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_
   return 4 * (n_txn + 1) + 9 * nnz + 16 * nnz + n_txn + (with_conflict ? 4 * n_txn : 0);
 }
 
+extern "C" uint64_t dcc_nowait_iso_alg_bytes(uint64_t n_txn, uint64_t nnz, uint64_t held_n, int with_conflict,
+                                             uint32_t flags) {
+  // READ_COMMITTED: a read still probes one slot.  READ_UNCOMMITTED without held rows builds no table.
+  const uint64_t all = dcc_nowait_alg_bytes(n_txn, nnz, with_conflict);
+  const bool ru = (flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED)) == DCC_ISO_READ_UNCOMMITTED;
+  return ru && held_n == 0 ? all - 16 * nnz : all;
+}
+
 extern "C" int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const dcc_calvin_held* held,
                                      uint8_t* out_rc, uint32_t* out_conflict, dcc_stats* out_stats) {
   if (!ctx || !batch || !out_rc) return DCC_EINVAL;
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
-  if (ctx->multi && (batch->flags & DCC_SHARD_SELF) && dcc_multi_size(ctx) > 1)  // key-sharded over the ranks
+  if (ctx->multi && (batch->flags & DCC_SHARD_SELF) && dcc_multi_size(ctx) > 1) {  // key-sharded over the ranks
+    if (batch->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
+      return ctx->fail(DCC_ENOTSUP, "nowait: a key-sharded epoch is SERIALIZABLE only");
     return dcc_multi_nowait_epoch(ctx, batch, held, out_rc, out_conflict, out_stats);
+  }
   if (ctx->multi)  // without the flag: the whole epoch on rank 0, no collective
     return dcc_multi_on_rank0(ctx, true, [&](dcc_ctx* s) {
       return s->nowait_epoch(batch, held, out_rc, out_conflict, out_stats);

@@ -848,6 +848,9 @@ extern "C" uint64_t dcc_waitdie_alg_bytes(uint64_t n_txn, uint64_t nnz, int with
 extern "C" int dcc_waitdie_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* rc,
                                       uint32_t* pos, uint32_t* out_conflict, dcc_stats* out_stats) {
   if (!ctx || !batch || !ts || !rc || !pos) return DCC_EINVAL;
+  // a read released inside the epoch would promote waiters mid-epoch: SERIALIZABLE only
+  if (batch->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
+    return ctx->fail(DCC_ENOTSUP, "waitdie: an isolation level below SERIALIZABLE");
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
   // a multi-GPU context: the whole epoch on rank 0, no collective
   return dcc_on_device(ctx, true,
@@ -858,6 +861,8 @@ extern "C" int dcc_waitdie_release(dcc_ctx* ctx, const dcc_batch* batch, const u
                                    uint32_t* pos, const uint8_t* leave, uint64_t* out_left,
                                    uint64_t* out_promoted, dcc_stats* out_stats) {
   if (!ctx || !batch || !ts || !rc || !pos || !leave) return DCC_EINVAL;
+  if (batch->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
+    return ctx->fail(DCC_ENOTSUP, "waitdie: an isolation level below SERIALIZABLE");
   dcc_pipe_drain(ctx);
   return dcc_on_device(ctx, true, [&](dcc_ctx* s) {
     return s->waitdie_release(batch, ts, rc, pos, leave, out_left, out_promoted, out_stats);

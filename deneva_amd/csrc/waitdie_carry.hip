@@ -500,6 +500,9 @@ extern "C" uint64_t dcc_waitdie_carry_alg_bytes(uint64_t n_txn, uint64_t n_kept,
 extern "C" int dcc_waitdie_carry(dcc_ctx* ctx, const dcc_waitdie_carry_args* a, uint64_t* out_n, uint64_t* out_nnz,
                                  uint64_t* out_kept, dcc_stats* out_stats) {
   if (!ctx) return DCC_EINVAL;
+  if (a && (((a->batch ? a->batch->flags : 0u) | (a->fresh ? a->fresh->flags : 0u)) &
+            (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED)))
+    return ctx->fail(DCC_ENOTSUP, "waitdie: an isolation level below SERIALIZABLE");
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
   // a local data movement: rank 0's GPU, its communicator left alone
   return dcc_on_device(ctx, false,

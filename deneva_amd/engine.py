@@ -464,7 +464,8 @@ class Engine:
 
     # ------------------------------------------------------ NO_WAIT (2PL)
     def nowait_lock_epoch(self, batch: EpochBatch, held=None, want_conflict: bool = True,
-                          out_rc=None, out_conflict=None, shard: bool = False):
+                          out_rc=None, out_conflict=None, shard: bool = False,
+                          isolation: int = _abi.ISO_SERIALIZABLE):
         """NO_WAIT lock acquisition of an epoch (dcc_nowait_lock_epoch): returns
         (rc u8[n], conflict u32[n] | None, stats).  held = (keys u64[h],
         acctype u8[h]): rows still locked by txns of earlier epochs.
@@ -472,7 +473,9 @@ class Engine:
         ACCESS_NONE for a committed one.  shard: on a multi-GPU engine or one
         with a communicator the epoch is key-sharded across the ranks
         (DCC_SHARD_SELF): every rank passes this whole batch and held list and
-        gets the whole outputs."""
+        gets the whole outputs.  isolation: ISO_SERIALIZABLE, ISO_READ_COMMITTED
+        (a read lock is released right after the read) or ISO_READ_UNCOMMITTED
+        (every lock is released right after its access)."""
         n = batch.n_txn
         dev = batch.on_device
         if dev:
@@ -492,7 +495,7 @@ class Engine:
         if out_rc.shape[0] < n or (out_conflict is not None and out_conflict.shape[0] < n):
             raise ValueError("nowait_lock_epoch: output buffer shorter than the epoch")
         st = _abi.Stats()
-        b = batch.to_c(_abi.SHARD_SELF if shard else 0)
+        b = batch.to_c((_abi.SHARD_SELF if shard else 0) | int(isolation))
         h = None
         if held is not None:
             hk, ha = held
@@ -1161,10 +1164,13 @@ class LockTable:
             raise ValueError("lock table is closed")
         return self._q
 
-    def lock_epoch(self, batch: EpochBatch, want_conflict: bool = True, out_rc=None, out_conflict=None):
+    def lock_epoch(self, batch: EpochBatch, want_conflict: bool = True, out_rc=None, out_conflict=None,
+                   isolation: int = _abi.ISO_SERIALIZABLE):
         """The epoch against the table's rows; the requests of its committed
         txns stay in the table (dcc_locktab_lock_epoch).  Returns (rc u8[n],
-        conflict u32[n] | None, stats) as Engine.nowait_lock_epoch."""
+        conflict u32[n] | None, stats) as Engine.nowait_lock_epoch.  isolation:
+        at ISO_READ_COMMITTED only the EX requests of the committed txns stay,
+        at ISO_READ_UNCOMMITTED none."""
         n = batch.n_txn
         if batch.on_device:
             import torch
@@ -1183,23 +1189,26 @@ class LockTable:
         if out_rc.shape[0] < n or (out_conflict is not None and out_conflict.shape[0] < n):
             raise ValueError("lock_epoch: output buffer shorter than the epoch")
         st = _abi.Stats()
-        b = batch.to_c()
+        b = batch.to_c(int(isolation))
         _check(lib.dcc_locktab_lock_epoch(self._handle(), C.byref(b), _ptr(out_rc), _ptr(out_conflict),
                                           C.byref(st)), self._eng._h)
         return out_rc[:n], (out_conflict[:n] if want_conflict else None), st.as_dict()
 
-    def release(self, batch: EpochBatch, rc=None, want: int = _abi.RC_RCOK):
+    def release(self, batch: EpochBatch, rc=None, want: int = _abi.RC_RCOK,
+                isolation: int = _abi.ISO_SERIALIZABLE):
         """lock_release for every access of the txns with rc[i] == want (rc
         None: of every txn) (dcc_locktab_release): returns (n, nnz, stats) of
         what was released.  A row released more often than it is held raises
-        DccError(DCC_EINVAL) and leaves the table unchanged."""
+        DccError(DCC_EINVAL) and leaves the table unchanged.  isolation: the
+        level the txns ran at: ISO_READ_COMMITTED releases their EX accesses
+        only, ISO_READ_UNCOMMITTED nothing."""
         if rc is not None:
             if not batch.on_device:
                 rc = np.ascontiguousarray(rc, np.uint8)
             if rc.shape[0] < batch.n_txn:
                 raise ValueError("release: rc shorter than the epoch")
         st = _abi.Stats()
-        b = batch.to_c()
+        b = batch.to_c(int(isolation))
         ns, ms = C.c_uint64(0), C.c_uint64(0)
         _check(lib.dcc_locktab_release(self._handle(), C.byref(b), _ptr(rc), want, C.byref(ns), C.byref(ms),
                                        C.byref(st)), self._eng._h)
@@ -1307,6 +1316,11 @@ def calvin_alg_bytes(n_txn: int, nnz: int, with_order: bool, with_wave: bool) ->
 
 def nowait_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
     return int(lib.dcc_nowait_alg_bytes(n_txn, nnz, int(with_conflict)))
+
+
+def nowait_iso_alg_bytes(n_txn: int, nnz: int, held_n: int = 0, with_conflict: bool = True,
+                         isolation: int = _abi.ISO_SERIALIZABLE) -> int:
+    return int(lib.dcc_nowait_iso_alg_bytes(n_txn, nnz, held_n, int(with_conflict), int(isolation)))
 
 
 def tso_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:

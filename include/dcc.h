@@ -97,6 +97,17 @@ extern "C" {
  * without it that call is not key-sharded at all.  On a context that is not
  * key-sharded the flag is ignored. */
 #define DCC_SHARD_SELF 0x80u
+/* ISOLATION_LEVEL of a 2PL NO_WAIT epoch (config.h; ycsb_txn.cpp:233-236,
+ * 248-251, txn.cpp:692-726).  Neither bit: SERIALIZABLE.  Both: DCC_EINVAL.
+ * The level is a property of the epoch, not of a context or a lock table.
+ * dcc_nowait_lock_epoch, dcc_locktab_lock_epoch and dcc_locktab_release honour
+ * the bits (their comments have the contract); dcc_waitdie_lock_epoch,
+ * dcc_waitdie_release and dcc_waitdie_carry are DCC_ENOTSUP with one set (a
+ * read released inside a WAIT_DIE epoch would promote waiters mid-epoch).
+ * Every other entry point ignores them: OCC, TIMESTAMP, MVCC, MaaT and Calvin
+ * are not modelled below SERIALIZABLE. */
+#define DCC_ISO_READ_COMMITTED 0x100u   /* a read lock is released right after the read   */
+#define DCC_ISO_READ_UNCOMMITTED 0x200u /* every lock is released right after its access  */
 
 /* One epoch as a CSR of per-transaction access lists in capture order
  * (Access list of TxnManager, system/txn.h:39-70; txn.cpp:818-847). */
@@ -492,8 +503,25 @@ int dcc_calvin_order_epoch_held(dcc_ctx* ctx, const dcc_batch* batch, const dcc_
  * flag says), exchanging in list order instead of n_txn bytes per round, and
  * pipelining sharded epochs; TIMESTAMP, MVCC, WAIT_DIE and MaaT are not
  * key-sharded.
+ * Isolation (DCC_ISO_* in batch->flags): the same replay with the reference's
+ * early releases, the YCSB behaviour for every batch (TPC-C in the reference
+ * never calls release_last_row_lock; that leak is not modelled).
+ *   READ_COMMITTED    a granted RD/SCAN is released at once, so a read never
+ *                     blocks a later writer; an abort releases the txn's EX
+ *                     rows, a committed txn holds its EX rows.  Within a txn
+ *                     RD then WR of one row is fine, WR then RD and WR then WR
+ *                     abort at the second.
+ *   READ_UNCOMMITTED  every granted lock is released at once: a txn aborts
+ *                     only on the held prefix (a row EX-held, or held and the
+ *                     access EX); without `held` every txn commits.  rounds 0.
+ * `held` stays a literal statement of the table before txn 0 at every level
+ * (an SH entry is an SH lock): a READ_COMMITTED caller passes what its earlier
+ * txns still hold, their EX rows.  An isolation bit on an epoch that would run
+ * key-sharded (DCC_SHARD_SELF on a communicator of more than one rank, on
+ * DCC_OPT_COMM_SOLO, or on a dcc_init_multi context of more than one rank) is
+ * DCC_ENOTSUP on every rank, before any collective.
  * Stats: n_commit, n_abort, nnz_w (EX requests), n_readonly (txns with no EX
- * request), rounds, device_ms, total_ms, alg_bytes (dcc_nowait_alg_bytes);
+ * request), rounds, device_ms, total_ms, alg_bytes (dcc_nowait_iso_alg_bytes);
  * with profiling phase_ms: 0 = table build, 1 = round 1, 2 = rounds >= 2,
  * 3 = RC / conflict pass. */
 #define DCC_ACCESS_NONE 0xFFFFFFFFu
@@ -502,6 +530,11 @@ int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const dcc_calvin
 /* Algorithmic bytes of one NO_WAIT epoch: 4(N+1) offsets + 9 nnz (key, type)
  * + 16 nnz (one lock-table slot per request) + N (RC) [+ 4N conflict]. */
 uint64_t dcc_nowait_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
+/* The same at the level in `flags` (DCC_ISO_*): SERIALIZABLE and
+ * READ_COMMITTED equal dcc_nowait_alg_bytes (a read still probes one slot);
+ * READ_UNCOMMITTED drops the 16 nnz when held_n == 0 (no table is built). */
+uint64_t dcc_nowait_iso_alg_bytes(uint64_t n_txn, uint64_t nnz, uint64_t held_n, int with_conflict,
+                                  uint32_t flags);
 
 /* ------------------------------------------------ TIMESTAMP (basic T/O) */
 /* Epoch under CC_ALG TIMESTAMP with one txn in flight at a time: the result
@@ -840,6 +873,17 @@ uint64_t dcc_waitdie_carry_alg_bytes(uint64_t n_txn, uint64_t n_kept, uint64_t n
  * the others, alg_bytes (dcc_locktab_release_alg_bytes), device_ms, total_ms;
  * with profiling phase_ms: 0 = offsets check, 1 = scratch add, 2 = compare,
  * 3 = apply.
+ *
+ * Isolation (DCC_ISO_* in batch->flags, per call: one table may see epochs of
+ * different levels).  dcc_locktab_lock_epoch decides as dcc_nowait_lock_epoch
+ * does at that level; of a committed txn every request stays (SERIALIZABLE),
+ * only the EX requests (READ_COMMITTED: the incoming requests of the room rule
+ * below are the EX ones), or none (READ_UNCOMMITTED: the table is unchanged).
+ * dcc_locktab_release releases every access of a selected txn, only its EX
+ * accesses, or none (a valid no-op); *out_nnz counts the accesses released,
+ * *out_n the selected txns, and the over-release rule is unchanged.  Both bits
+ * together are DCC_EINVAL.  dcc_locktab_acquire_rows, dcc_locktab_release_rows
+ * and dcc_locktab_export know no level.
  *
  * dcc_locktab_acquire_rows takes a plain (key, access type) list as the held
  * prefix of dcc_nowait_lock_epoch does: a row is EX if any of its entries is

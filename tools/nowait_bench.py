@@ -6,6 +6,7 @@ batches: the C2 shape (65,536 x 16, theta 0.9) and the headline shape
 
     python tools/nowait_bench.py [--warmup 5] [--steps 20] [--shape both|c2|headline]
                                  [--check-1m] [--json PATH] [--shards R]
+                                 [--isolation ser|rc|ru|all]
 
 device_ms is the engine's own device time of the decision (HIP events on its
 stream around the kernels of one call, batch resident); the table reports the
@@ -20,7 +21,13 @@ host, so the figures show what sharding costs and how much smaller a rank's
 lock table is, not how it scales.  R = 1 is the unflagged epoch on one
 context.  device_ms is the maximum over the ranks; the collectives come from
 dcc_comm_calls, the table bytes from the sizing rule (16-byte slots, the next
-power of two above 1.25 x the rank's own requests, at least 1,024)."""
+power of two above 1.25 x the rank's own requests, at least 1,024).
+
+--isolation times the epoch at the isolation levels (DCC_ISO_*, DESIGN.md
+§8q): the levels chosen and the OCC round solver alternate call by call in one
+process on the same resident batches; parity with the levels' replay
+(tests/nowait_iso_ref.py) is checked on the C2 shape after timing, and every
+result carries its level."""
 import argparse
 import json
 import os
@@ -37,6 +44,8 @@ import torch  # noqa: E402
 import deneva_amd as d  # noqa: E402
 from deneva_amd import _abi  # noqa: E402
 from nowait_ref import replay  # noqa: E402  (checker only)
+
+ISO = {"ser": d.ISO_SERIALIZABLE, "rc": d.ISO_READ_COMMITTED, "ru": d.ISO_READ_UNCOMMITTED}
 
 
 def summary(stats):
@@ -100,6 +109,72 @@ def run_shards(a):
     return out
 
 
+def run_isolation(a):
+    from nowait_iso_ref import replay as iso_replay  # checker only
+    levels = list(ISO) if a.isolation == "all" else [a.isolation]
+    out = {}
+    with d.Engine(0) as eng:
+        for name, n in (("C2 65,536 x 16", 65536), ("headline 1,048,576 x 16", 1 << 20)):
+            if a.shape != "both" and (a.shape == "c2") != (n == 65536):
+                continue
+            b = d.gen_ycsb(n_txn=n, zipf_theta=0.9)
+            db = b.to_torch("cuda:0")
+            rc = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+            cf = torch.empty(n, dtype=torch.int32, device="cuda:0")
+            orc = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+            eng.reserve(b.n_txn, b.nnz)
+
+            def nowait(lv):
+                return eng.nowait_lock_epoch(db, out_rc=rc, out_conflict=cf, isolation=ISO[lv])[2]
+
+            def occ():
+                return eng.occ_validate_epoch(db, out_rc=orc)[2]
+
+            eng.set_option(_abi.OPT_SOLVER, 1)
+            for _ in range(a.warmup):
+                for lv in levels:
+                    nowait(lv)
+                occ()
+            st = {lv: [] for lv in levels}
+            st_o = []
+            for _ in range(a.steps):  # alternate, so that all see the same machine state
+                for lv in levels:
+                    st[lv].append(nowait(lv))
+                st_o.append(occ())
+            torch.cuda.synchronize()
+            res = {lv: dict(summary(st[lv]), isolation=lv) for lv in levels}
+            res["occ_rounds"] = summary(st_o)
+            eng.set_profiling(True)
+            for lv in levels:
+                ph = [nowait(lv)["phase_ms"] for _ in range(5)]
+                res[lv]["phase_ms"] = [statistics.median(p[q] for p in ph) for q in range(4)]
+            eng.set_profiling(False)
+            eng.set_option(_abi.OPT_SOLVER, 0)
+            for lv in levels:
+                res[lv]["ratio_to_occ_rounds"] = res[lv]["device_ms"] / res["occ_rounds"]["device_ms"]
+                if "ser" in res:
+                    res[lv]["ratio_to_ser"] = res[lv]["device_ms"] / res["ser"]["device_ms"]
+                if n == 65536 or a.check_1m:
+                    erc, ecf = iso_replay(b, None, ISO[lv])
+                    nowait(lv)
+                    res[lv]["parity_vs_replay"] = bool(
+                        np.array_equal(rc.cpu().numpy(), erc)
+                        and np.array_equal(cf.cpu().numpy().view(np.uint32), ecf))
+            out[name] = res
+            print(f"{name}:")
+            for lv in levels:
+                r = res[lv]
+                print(f"  {lv:10s} device_ms {r['device_ms']:.3f} (min {r['device_ms_min']:.3f}, "
+                      f"max {r['device_ms_max']:.3f})  rounds {r['rounds']}  "
+                      f"commits {r['n_commit']}  aborts {r['n_abort']}  "
+                      f"phase_ms {[round(x, 3) for x in r['phase_ms']]}  x OCC rounds {r['ratio_to_occ_rounds']:.2f}"
+                      + (f"  parity_vs_replay {r['parity_vs_replay']}" if "parity_vs_replay" in r else ""))
+            r = res["occ_rounds"]
+            print(f"  occ_rounds device_ms {r['device_ms']:.3f} (min {r['device_ms_min']:.3f}, "
+                  f"max {r['device_ms_max']:.3f})  rounds {r['rounds']}")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -110,14 +185,19 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--shards", type=int, default=0,
                     help="time the key-sharded epoch on R ranks sharing cuda:0 (1: the unflagged epoch)")
+    ap.add_argument("--isolation", choices=("ser", "rc", "ru", "all"), default=None,
+                    help="time the epoch at these isolation levels, alternating in one process")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "nowait_bench needs cuda:0"
+    assert not (a.shards and a.isolation), "a key-sharded epoch is SERIALIZABLE only"
     out = {}
     if a.shards:
         out = run_shards(a)
+    if a.isolation:
+        out = run_isolation(a)
     with d.Engine(0) as eng:
         for name, n in (("C2 65,536 x 16", 65536), ("headline 1,048,576 x 16", 1 << 20)):
-            if a.shards or (a.shape != "both" and (a.shape == "c2") != (n == 65536)):
+            if a.shards or a.isolation or (a.shape != "both" and (a.shape == "c2") != (n == 65536)):
                 continue
             b = d.gen_ycsb(n_txn=n, zipf_theta=0.9)
             db = b.to_torch("cuda:0")
@@ -173,7 +253,8 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1)
-    assert all(r.get("parity_vs_replay", True) for r in out.values()), "NO_WAIT differs from the replay"
+    flat = [x for r in out.values() for x in [r] + [v for v in r.values() if isinstance(v, dict)]]
+    assert all(x.get("parity_vs_replay", True) for x in flat), "NO_WAIT differs from the replay"
 
 
 if __name__ == "__main__":
