@@ -212,7 +212,7 @@ struct LtEpoch {
   const uint32_t* err = nullptr;   // the epoch's error word
   unsigned grid = 1;
   uint32_t mask = 0;   // the per-epoch table's
-  uint32_t level = 0;  // 0 SERIALIZABLE, 1 READ_COMMITTED, 2 READ_UNCOMMITTED
+  int level = 0;       // ISO_SER / ISO_RC / ISO_RU (nowait_lanes.h)
 };
 
 struct dcc_ctx {

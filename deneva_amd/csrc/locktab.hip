@@ -540,7 +540,7 @@ int dcc_ctx::locktab_seed(dcc_locktab* lt, const LtEpoch& E) {
   if (profiling) CK(hipEventRecord(pev[5], stream));
   LtSeed A{E.n,    E.off, E.keys, E.sid, E.tab, E.lp, (const LtSlot*)lt->tab[lt->cur].p, (uint32_t)(lt->n_slots - 1),
            E.mask, (uint32_t*)E.err};
-  if (E.level == 2) k_lt_seed<true><<<E.grid, NW_T, 0, stream>>>(A);
+  if (E.level == ISO_RU) k_lt_seed<true><<<E.grid, NW_T, 0, stream>>>(A);
   else k_lt_seed<false><<<E.grid, NW_T, 0, stream>>>(A);
   CK(hipGetLastError());
   return DCC_OK;
@@ -554,8 +554,8 @@ int dcc_ctx::locktab_grant(dcc_locktab* lt, const LtEpoch& E) {
             ctl};
   // fewer, longer workgroups than the epoch's passes: the combiner folds what one workgroup sees
   const unsigned grid = launch_grid(E.n, NW_T >> E.lp, (unsigned)n_cu * 4);
-  if (E.level == 1) k_lt_grant<true><<<grid, NW_T, 0, stream>>>(A);
-  else if (E.level == 0) k_lt_grant<false><<<grid, NW_T, 0, stream>>>(A);  // READ_UNCOMMITTED: nothing stays
+  if (E.level == ISO_RC) k_lt_grant<true><<<grid, NW_T, 0, stream>>>(A);
+  else if (E.level == ISO_SER) k_lt_grant<false><<<grid, NW_T, 0, stream>>>(A);  // READ_UNCOMMITTED: nothing stays
   CK(hipGetLastError());
   CK(hipMemcpyAsync((uint8_t*)hmisc + LT_HMISC_OFF, ctl, LT_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
   return DCC_OK;

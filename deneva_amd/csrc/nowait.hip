@@ -74,6 +74,21 @@
 // k_nw_final.  READ_UNCOMMITTED releases every lock after its access: no
 // access leaves a trace, k_nw_ru decides every txn against the held rows in
 // one pass, and without held rows no table is built.
+//
+// Host (the phase shape of DESIGN.md §8n): nw_plan resolves the call once into
+// an NwPlan -- key-sharded or not, the level, lock table or held list, when the
+// table is sized -- and makes every host-side rejection.  nowait_epoch is then
+// a sequence of phases over one NwRun:
+//           nw_table     the table for nw_rows(m, hn) rows, where they suffice
+//           nw_check     workspaces, the held list staged, k_batch_check next
+//                        to k_nw_count / k_nw_count_ex, the read-back
+//           nw_table     ... or for the rows the check counted (key-sharded;
+//                        READ_COMMITTED without a lock table)
+//           nw_build     ev0, locktab_begin, the table cleared, k_nw_held, the
+//                        build kernels, locktab_seed
+//           nw_decide    nw_rounds<SH, ISO>, the one round body of the three
+//                        modes with rounds, or k_nw_ru
+//           nw_readout   locktab_grant, ev1, the outputs, counts and stats
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -107,8 +122,6 @@ constexpr uint32_t SID_REMOTE = SID_NONE - 1;
 constexpr uint32_t SID_ABSENT = SID_NONE - 2;
 // the EX requests of the batch, counted next to the batch check
 constexpr uint32_t NW_C_EXREQ = 7;
-// the level of an epoch (a template parameter of the rounds' kernels)
-constexpr int ISO_SER = 0, ISO_RC = 1;
 // status bytes of a sharded round
 constexpr uint8_t NW_S_BLOCKED = 1, NW_S_KILLED = 2;
 
@@ -684,6 +697,257 @@ __global__ __launch_bounds__(NW_T) void k_nw_conf(uint64_t n, const uint8_t* __r
   }
 }
 
+// ------------------------------------------------------------------ host
+// What the call asks for, resolved once (nw_plan) before anything is staged.
+// The per-epoch table is sized from (m, hn) before the check, from the check's
+// counts after it, or not built at all (nw_rows).
+constexpr int NW_TAB_NONE = 0, NW_TAB_EARLY = 1, NW_TAB_LATE = 2;
+struct NwPlan {
+  bool sh = false;   // key-sharded: the batch is the whole epoch on every rank (DCC_SHARD_SELF)
+  bool lt = false;   // a lock table's held rows take the place of a held list
+  bool dev = false;  // DCC_DEVICE_PTRS
+  int iso = ISO_SER, tab = NW_TAB_EARLY;
+  uint32_t iso_bits = 0;  // the batch's DCC_ISO_* bits
+  uint64_t hn = 0;        // held rows
+};
+
+// One epoch's launch state (as tso_kernels.h's TsRun): the phases fill and read it.
+struct NwRun {
+  NwPlan P;
+  DevBatch d;
+  uint64_t n = 0, m = 0, cap = 0, nnz_ex = 0, per_block = 0;
+  uint32_t rounds = 0;
+  unsigned max_grid = 1;
+  uint32_t *cnt = nullptr, *ring = nullptr, *lists[2] = {}, *conf_dev = nullptr;
+  uint8_t* rc_dev = nullptr;
+  const uint64_t* hk = nullptr;  // the held list on the device
+  const uint8_t* ha = nullptr;
+  NwShArgs A{};  // the kernels that are not key-sharded take its NwArgs
+  LtEpoch L;
+};
+
+// Every host-side rejection of a call, in the order the caller sees them.
+int nw_plan(dcc_ctx* ctx, const dcc_batch* b, const dcc_calvin_held* held, bool lt, NwPlan& P) {
+  CR(ctx->check_batch(b, false));  // the offsets are checked on the device (k_batch_check)
+  // key-sharded: the batch is the whole epoch on every rank (DCC_SHARD_SELF); a lock table is one GPU's
+  P.lt = lt;
+  P.sh = !lt && ctx->sharded() && (b->flags & DCC_SHARD_SELF) != 0;
+  if (ctx->comm_ranks() > 1 && !P.sh)
+    return ctx->fail(DCC_ENOTSUP,
+                     "nowait: more than one rank takes the whole epoch with DCC_SHARD_SELF and no lock table");
+  P.iso_bits = b->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED);
+  if (P.iso_bits == (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
+    return ctx->fail(DCC_EINVAL, "nowait: both isolation bits set");
+  P.iso = P.iso_bits == DCC_ISO_READ_COMMITTED ? ISO_RC : P.iso_bits ? ISO_RU : ISO_SER;
+  if (P.sh && P.iso != ISO_SER)  // on every rank alike, before any collective
+    return ctx->fail(DCC_ENOTSUP, "nowait: a key-sharded epoch is SERIALIZABLE only");
+  P.hn = held ? held->n : 0;
+  if (lt && P.hn) return ctx->fail(DCC_EINVAL, "nowait: a held list next to a lock table");
+  if (P.hn && (!held->keys || !held->acctype)) return ctx->fail(DCC_EINVAL, "nowait: null held keys/acctype");
+  P.dev = (b->flags & DCC_DEVICE_PTRS) != 0;
+  if (b->n_txn >= (uint64_t)IDX_MASK)  // owner words carry index + 1
+    return ctx->fail(DCC_ERANGE, "nowait: n_txn %llu exceeds %u", (unsigned long long)b->n_txn, IDX_MASK - 1);
+  P.tab = P.sh || (P.iso == ISO_RC && !lt) ? NW_TAB_LATE : P.iso == ISO_RU && !lt && !P.hn ? NW_TAB_NONE : NW_TAB_EARLY;
+  return DCC_OK;
+}
+
+// The rows the per-epoch table must hold; `hc`: the check's counted words, of a
+// table sized late.  Key-sharded: the rank's own requests and held rows.  A lock
+// table: every request keeps a slot (k_lt_seed marks the held rows through
+// them; READ_UNCOMMITTED: of the table's rows at most one per request).
+// READ_COMMITTED: the held rows and the EX requests.  READ_UNCOMMITTED: the held
+// rows alone (NW_TAB_NONE without them).
+uint64_t nw_rows(const NwPlan& P, uint64_t m, const uint32_t* hc) {
+  if (P.sh) return (uint64_t)hc[NW_C_OWN] + hc[NW_C_OWNHELD];
+  if (P.lt) return m;
+  if (P.iso == ISO_RC) return (uint64_t)hc[NW_C_EXREQ] + P.hn;
+  return P.iso == ISO_RU ? P.hn : m + P.hn;
+}
+int nw_table(dcc_ctx* ctx, NwRun& R, uint64_t rows) {
+  R.cap = dcc_ctx::table_capacity(rows);
+  if (R.cap > (1ull << 30)) return ctx->fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
+  return ctx->table.ensure(ctx, R.cap * sizeof(Slot), "table");
+}
+
+// The workspaces, the held list on the device, and the check: a malformed
+// batch is rejected before anything indexes with its offsets (every rank
+// checks the whole batch and the whole held list: all reject alike, before any
+// collective).  Next to it the counts that size a late table.
+int nw_check(dcc_ctx* ctx, NwRun& R, const dcc_calvin_held* held, uint8_t* out_rc, uint32_t* out_conflict) {
+  const NwPlan& P = R.P;
+  hipStream_t stream = ctx->stream;
+  const uint64_t n = R.n, m = R.m;
+  CR(ctx->nowait_reserve(n, m, out_conflict != nullptr && !P.dev, false));
+  uint32_t* cnt = R.cnt = (uint32_t*)ctx->nw_misc.p;
+  R.ring = cnt + NW_C_RING;
+  R.lists[0] = (uint32_t*)ctx->nw_list.p;
+  R.lists[1] = R.lists[0] + n;
+  R.rc_dev = P.dev ? out_rc : (uint8_t*)ctx->rc.p;
+  R.conf_dev = out_conflict ? (P.dev ? out_conflict : (uint32_t*)ctx->nw_conf.p) : nullptr;
+  R.max_grid = (unsigned)ctx->n_cu * 16;
+  const NwOwn who{(uint32_t)ctx->comm_rank(), (uint32_t)ctx->comm_ranks()};
+  CR(ctx->stage_held(held, P.dev, R.hk, R.ha));
+
+  CK(hipMemsetAsync(cnt, 0, NW_C_WORDS * 4, stream));
+  k_batch_check<false><<<launch_grid(std::max(n, m), CHK_T * 4, R.max_grid), CHK_T, 0, stream>>>(
+      R.d.off, n, R.d.keys, m, cnt);
+  if (P.sh)
+    k_nw_count<<<launch_grid(std::max(m, P.hn), CHK_T * 4, R.max_grid), CHK_T, 0, stream>>>(R.d.keys, m, R.hk, P.hn,
+                                                                                          who, cnt);
+  if (P.iso == ISO_RC)
+    k_nw_count_ex<<<launch_grid(m, CHK_T * 4, R.max_grid), CHK_T, 0, stream>>>(R.d.acctype, m, cnt);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(ctx->hmisc, cnt, P.sh || P.iso == ISO_RC ? NW_C_RING * 4 : 8, hipMemcpyDeviceToHost, stream));
+  CK(hipStreamSynchronize(stream));
+  const uint32_t* hc = (const uint32_t*)ctx->hmisc;
+  BatchShape shape;
+  CR(batch_checked(ctx, hc, m, false, shape));
+  if (P.sh && (hc[SEG_C_ERR] & NW_ERR_HKEY))
+    return ctx->fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
+  R.nnz_ex = P.iso == ISO_RC ? hc[NW_C_EXREQ] : 0;
+  R.per_block = NW_T >> shape.lp;  // txns per workgroup step
+  R.A = NwShArgs{NwArgs{n, R.d.off, R.d.keys, R.d.acctype, nullptr, 0, shape.lp, (uint32_t*)ctx->nw_sid.p,
+                        (uint8_t*)ctx->state.p, cnt},
+                 who, (uint8_t*)ctx->nw_stat.p};  // tab and mask: nw_build
+  return DCC_OK;
+}
+
+// What the lock table's passes read of the epoch.
+LtEpoch nw_lt_epoch(const NwArgs& A, unsigned grid, int iso) {
+  return LtEpoch{A.n, A.off, A.keys, A.at, A.sid, A.state, A.tab, A.lp, &A.cnt[SEG_C_ERR], grid, A.mask, iso};
+}
+
+// The table: cleared, the held rows, every request (k_nw_ru looks the held
+// rows up itself: READ_UNCOMMITTED builds nothing).  A lock table's held rows
+// take the place of a held list: their tag-0 words (locktab_seed).
+int nw_build(dcc_ctx* ctx, NwRun& R, dcc_locktab* lt) {
+  const NwPlan& P = R.P;
+  hipStream_t stream = ctx->stream;
+  const uint64_t n = R.n, cap = R.cap;
+  CK(hipEventRecord(ctx->ev0, stream));
+  if (ctx->profiling) CK(hipEventRecord(ctx->pev[0], stream));
+  // room for every request that can stay, or DCC_ERANGE
+  if (lt) CR(ctx->locktab_begin(lt, P.iso == ISO_RC ? R.nnz_ex : P.iso == ISO_RU ? 0 : R.m, "lock epoch"));
+  Slot* tab = R.A.tab = cap ? (Slot*)ctx->table.p : nullptr;
+  const uint32_t mask = R.A.mask = (uint32_t)(cap - 1);
+  if (cap) CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
+  if (P.hn) {
+    const unsigned hgrid = launch_grid(P.hn, NW_T, R.max_grid);
+    if (P.sh) k_nw_held<true><<<hgrid, NW_T, 0, stream>>>(R.hk, R.ha, P.hn, tab, mask, R.cnt, R.A.who);
+    else k_nw_held<false><<<hgrid, NW_T, 0, stream>>>(R.hk, R.ha, P.hn, tab, mask, R.cnt, NwAll{});
+  }
+  const unsigned grid = launch_grid(n, R.per_block, R.max_grid);
+  if (P.sh) {
+    CK(hipMemsetAsync(R.A.stat, 0, n, stream));  // every pass that sets a byte clears it again
+    k_nw_build<true><<<grid, NW_T, 0, stream>>>(R.A);
+  } else if (P.iso == ISO_RC) {
+    k_nw_build_ex<<<grid, NW_T, 0, stream>>>(R.A);
+    k_nw_build_rd<<<grid, NW_T, 0, stream>>>(R.A, lt != nullptr);
+  } else if (P.iso == ISO_SER) {
+    k_nw_build<false><<<grid, NW_T, 0, stream>>>(R.A);
+  }
+  CK(hipGetLastError());
+  if (lt) {
+    R.L = nw_lt_epoch(R.A, grid, P.iso);
+    CR(ctx->locktab_seed(lt, R.L));
+  }
+  if (ctx->profiling) CK(hipEventRecord(ctx->pev[1], stream));
+  return DCC_OK;
+}
+
+// The rounds (seg_rounds.h's loop): decide(r) reads its list length `left` and
+// appends the blocked txns to the list whose length word publish(r) cleared
+// (the whole ring is clear before round 1, which takes every txn and clears
+// nothing).  Rounds past the fixed point find empty lists.  `bound` sizes the
+// grids.  Then the RC bytes and the conflict ordinals.
+// Key-sharded, the state bytes and so the ring are the same on every rank:
+// every rank enqueues the same rounds, the ones past the fixed point too, and
+// each of them makes its one exchange.
+template <bool SH, int ISO>
+int nw_rounds(dcc_ctx* ctx, NwRun& R) {
+  static_assert(!(SH && ISO != ISO_SER), "a key-sharded epoch is SERIALIZABLE only");
+  hipStream_t stream = ctx->stream;
+  const NwA<SH> A = R.A;  // the lambda's arguments in locals, as they were
+  uint32_t* lists[2] = {R.lists[0], R.lists[1]};
+  const uint64_t n = R.n, cap = R.cap, per_block = R.per_block;
+  const unsigned max_grid = R.max_grid;
+  // READ_COMMITTED: one more round than SERIALIZABLE at most: the words of the self-aborted txns
+  const uint64_t max_r = n + (ISO == ISO_RC ? 3 : 2);
+  auto round = [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
+    const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;  // tags 62 .. 1, then again
+    const uint32_t tag = round_tag(er);
+    const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
+    const unsigned grid = launch_grid(bound, per_block, max_grid);
+    if (r > 1) {
+      if (er == 1)  // tag space exhausted: drop the tagged words, every undecided txn republishes
+        k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(A.tab, cap);
+      k_nw_publish<SH, ISO><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, left_out);
+    }
+    if constexpr (SH) {  // evaluate / all-reduce / apply; the collective can fail
+      k_nw_decide<NW_EVAL><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, nullptr, nullptr);
+      CR(ctx->comm_allreduce_max_u8(A.stat, n));
+      k_nw_decide<NW_APPLY><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
+      return DCC_OK;
+    } else {
+      k_nw_decide<NW_ONE, ISO><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
+    }
+  };
+  CR(rounds_loop(ctx, R.ring, n, max_r, "nowait", R.rounds, round));
+  k_nw_final<SH, ISO><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, R.rc_dev, R.conf_dev);
+  if constexpr (SH) {
+    if (R.conf_dev) {  // the lowest conflicting ordinal over the ranks
+      CR(ctx->comm_allreduce_max_u8(A.stat, n));
+      k_nw_conf<<<launch_grid(n, NW_T * 4, max_grid), NW_T, 0, stream>>>(n, A.state, A.stat, R.conf_dev, R.cnt);
+    }
+  }
+  return DCC_OK;
+}
+
+int nw_decide(dcc_ctx* ctx, NwRun& R) {
+  if (R.P.sh) return nw_rounds<true, ISO_SER>(ctx, R);
+  if (R.P.iso == ISO_RC) return nw_rounds<false, ISO_RC>(ctx, R);
+  if (R.P.iso == ISO_SER) return nw_rounds<false, ISO_SER>(ctx, R);
+  // READ_UNCOMMITTED, no rounds: one pass against the held rows
+  hipStream_t stream = ctx->stream;
+  if (ctx->profiling) CK(hipEventRecord(ctx->pev[2], stream));
+  k_nw_ru<<<launch_grid(R.n, R.per_block, R.max_grid), NW_T, 0, stream>>>(R.A, R.rc_dev, R.conf_dev);
+  if (ctx->profiling) CK(hipEventRecord(ctx->pev[3], stream));
+  return DCC_OK;
+}
+
+// The lock table's grants, the outputs and the counts.
+int nw_readout(dcc_ctx* ctx, NwRun& R, dcc_locktab* lt, uint8_t* out_rc, uint32_t* out_conflict, EpochStats& es) {
+  hipStream_t stream = ctx->stream;
+  const uint64_t n = R.n;
+  dcc_stats& S = es.S;
+  CK(hipGetLastError());
+  if (lt) CR(ctx->locktab_grant(lt, R.L));  // the committed txns' requests stay in the table
+  if (ctx->profiling) CK(hipEventRecord(ctx->pev[4], stream));
+  CK(hipEventRecord(ctx->ev1, stream));
+  if (!R.P.dev) {
+    CK(hipMemcpyAsync(out_rc, R.rc_dev, n, hipMemcpyDeviceToHost, stream));
+    if (out_conflict) CK(hipMemcpyAsync(out_conflict, R.conf_dev, n * 4, hipMemcpyDeviceToHost, stream));
+  }
+  CK(hipMemcpyAsync(ctx->hmisc, R.cnt, NW_C_RING * 4, hipMemcpyDeviceToHost, stream));
+  CK(hipStreamSynchronize(stream));
+  const uint32_t* hc = (const uint32_t*)ctx->hmisc;
+  if (hc[SEG_C_ERR] & CHK_ERR_KEY) return ctx->fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
+  if (hc[SEG_C_ERR] & NW_ERR_FULL) return ctx->fail(DCC_EIO, "nowait: lock table full");
+  if (hc[SEG_C_ERR] & NW_ERR_STATE) return ctx->fail(DCC_EIO, "nowait: inconsistent decisions");
+  S.rounds = R.rounds;
+  S.n_commit = hc[NW_C_COMMIT];
+  S.n_abort = n - hc[NW_C_COMMIT];
+  S.nnz_w = hc[NW_C_NEX];
+  S.n_readonly = hc[NW_C_RO];
+  S.alg_bytes = dcc_nowait_iso_alg_bytes(n, R.m, R.P.hn, out_conflict != nullptr, R.P.iso_bits);
+  if (lt) {
+    uint64_t granted = 0;
+    CR(ctx->locktab_end(lt, &granted));
+    S.alg_bytes = dcc_locktab_epoch_alg_bytes(n, R.m, granted, out_conflict != nullptr);
+  }
+  return es.finish(ctx, 4);
+}
+
 }  // namespace
 
 int dcc_ctx::nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict, bool whole_table) {
@@ -698,227 +962,29 @@ int dcc_ctx::nowait_reserve(uint64_t n, uint64_t nnz, bool with_conflict, bool w
   return DCC_OK;
 }
 
+// The epoch as phases over one NwRun: plan / table (sized early) / check and
+// count / table (sized late) / build / rounds / read-out.
 int dcc_ctx::nowait_epoch(const dcc_batch* b, const dcc_calvin_held* held, uint8_t* out_rc,
                           uint32_t* out_conflict, dcc_stats* st, dcc_locktab* lt) {
-  dcc_ctx* ctx = this;
   EpochStats es;
-  dcc_stats& S = es.S;
   if (!out_rc) return fail(DCC_EINVAL, "nowait: null out_rc");
-  CR(check_batch(b, false));  // the offsets are checked on the device (k_batch_check)
-  // key-sharded: the batch is the whole epoch on every rank (DCC_SHARD_SELF); a lock table is one GPU's
-  const bool sh = !lt && sharded() && (b->flags & DCC_SHARD_SELF) != 0;
-  if (comm_ranks() > 1 && !sh)
-    return fail(DCC_ENOTSUP, "nowait: more than one rank takes the whole epoch with DCC_SHARD_SELF and no lock table");
-  const uint32_t iso = b->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED);
-  if (iso == (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
-    return fail(DCC_EINVAL, "nowait: both isolation bits set");
-  const bool rcl = iso == DCC_ISO_READ_COMMITTED, rul = iso == DCC_ISO_READ_UNCOMMITTED;
-  if (sh && iso)  // on every rank alike, before any collective
-    return fail(DCC_ENOTSUP, "nowait: a key-sharded epoch is SERIALIZABLE only");
-  if (sh) S.n_shards = (uint32_t)comm_ranks();
-  const uint64_t hn = held ? held->n : 0;
-  if (lt && hn) return fail(DCC_EINVAL, "nowait: a held list next to a lock table");
-  if (hn && (!held->keys || !held->acctype)) return fail(DCC_EINVAL, "nowait: null held keys/acctype");
-  const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
+  NwRun R;
+  CR(nw_plan(this, b, held, lt != nullptr, R.P));
+  if (R.P.sh) es.S.n_shards = (uint32_t)comm_ranks();
   if (b->n_txn == 0) {
-    if (st) *st = S;
+    if (st) *st = es.S;
     return DCC_OK;
   }
-  if (b->n_txn >= (uint64_t)IDX_MASK)  // owner words carry index + 1
-    return fail(DCC_ERANGE, "nowait: n_txn %llu exceeds %u", (unsigned long long)b->n_txn, IDX_MASK - 1);
-  DevBatch d;
-  CR(stage_batch(b, d));
-  const uint64_t n = d.n, m = d.nnz;
-  // key-sharded: the rank's own requests and held rows size the table, once they are counted below
-  // READ_COMMITTED: the held rows and the EX requests, once they are counted; with a lock table every
-  // request keeps a slot (k_lt_seed marks the held rows through them).  READ_UNCOMMITTED: the held rows
-  // alone, no table without them; of a lock table's rows at most one per request.
-  const bool late = sh || (rcl && !lt);
-  uint64_t cap = late ? 0 : rul ? (lt ? table_capacity(m) : hn ? table_capacity(hn) : 0) : table_capacity(m + hn);
-  if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
-  CR(nowait_reserve(n, m, out_conflict != nullptr && !dev, !sh && !iso));
-  if (!late && cap) CR(table.ensure(this, cap * sizeof(Slot), "table"));
-  uint32_t* cnt = (uint32_t*)nw_misc.p;
-  uint32_t* ring = cnt + NW_C_RING;
-  uint32_t* lists[2] = {(uint32_t*)nw_list.p, (uint32_t*)nw_list.p + n};
-  uint8_t* rc_dev = dev ? out_rc : (uint8_t*)rc.p;
-  uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)nw_conf.p) : nullptr;
-  const unsigned max_grid = (unsigned)n_cu * 16;
-  const NwOwn who{(uint32_t)comm_rank(), (uint32_t)comm_ranks()};
-  const uint64_t* hk = nullptr;
-  const uint8_t* ha = nullptr;
-  if (sh && hn) CR(stage_held(held, dev, hk, ha));
-
-  // reject a malformed batch before anything indexes with its offsets (every
-  // rank checks the whole batch and the whole held list: all reject alike,
-  // before any collective)
-  CK(hipMemsetAsync(cnt, 0, NW_C_WORDS * 4, stream));
-  k_batch_check<false><<<launch_grid(std::max(n, m), CHK_T * 4, max_grid), CHK_T, 0, stream>>>(
-      d.off, n, d.keys, m, cnt);
-  if (sh)
-    k_nw_count<<<launch_grid(std::max(m, hn), CHK_T * 4, max_grid), CHK_T, 0, stream>>>(d.keys, m, hk, hn, who, cnt);
-  if (rcl) k_nw_count_ex<<<launch_grid(m, CHK_T * 4, max_grid), CHK_T, 0, stream>>>(d.acctype, m, cnt);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(hmisc, cnt, sh || rcl ? NW_C_RING * 4 : 8, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  BatchShape shape;
-  CR(batch_checked(this, (const uint32_t*)hmisc, m, false, shape));
-  if (sh) {
-    const uint32_t* hc = (const uint32_t*)hmisc;
-    if (hc[SEG_C_ERR] & NW_ERR_HKEY) return fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
-    cap = table_capacity((uint64_t)hc[NW_C_OWN] + hc[NW_C_OWNHELD]);
-    if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
-    CR(table.ensure(this, cap * sizeof(Slot), "table"));
-  }
-  const uint64_t nnz_ex = rcl ? ((const uint32_t*)hmisc)[NW_C_EXREQ] : 0;
-  if (rcl && !lt) {
-    cap = table_capacity(nnz_ex + hn);
-    if (cap > (1ull << 30)) return fail(DCC_ERANGE, "nowait: table capacity exceeds 2^30 slots");
-    CR(table.ensure(this, cap * sizeof(Slot), "table"));
-  }
-  const uint32_t mask = (uint32_t)(cap - 1);
-  const uint32_t lp = shape.lp;
-  const uint64_t per_block = NW_T >> lp;  // txns per workgroup step
-
-  const bool prof = profiling;
-  CK(hipEventRecord(ev0, stream));
-  if (prof) CK(hipEventRecord(pev[0], stream));
-  // room for every request that can stay, or DCC_ERANGE
-  if (lt) CR(locktab_begin(lt, rcl ? nnz_ex : rul ? 0 : m, "lock epoch"));
-  Slot* tab = cap ? (Slot*)table.p : nullptr;
-  if (cap) CK(hipMemsetAsync(tab, 0xFF, cap * sizeof(Slot), stream));
-  if (hn) {
-    if (sh) {
-      k_nw_held<true><<<launch_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt, who);
-    } else {
-      CR(stage_held(held, dev, hk, ha));
-      k_nw_held<false><<<launch_grid(hn, NW_T, max_grid), NW_T, 0, stream>>>(hk, ha, hn, tab, mask, cnt, NwAll{});
-    }
-  }
-  NwArgs A{n, d.off, d.keys, d.acctype, tab, mask, lp, (uint32_t*)nw_sid.p, (uint8_t*)state.p, cnt};
-  NwShArgs AS{A, who, (uint8_t*)nw_stat.p};
-  if (sh) {
-    CK(hipMemsetAsync(AS.stat, 0, n, stream));  // every pass that sets a byte clears it again
-    k_nw_build<true><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(AS);
-  } else if (rcl) {
-    k_nw_build_ex<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
-    k_nw_build_rd<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, lt != nullptr);
-  } else if (rul) {  // nothing to build: k_nw_ru looks the held rows up
-  } else {
-    k_nw_build<false><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A);
-  }
-  CK(hipGetLastError());
-  // the table's held rows take the place of a held list: their tag-0 words
-  LtEpoch L;
-  if (lt) {
-    L.n = n;
-    L.off = d.off;
-    L.keys = d.keys;
-    L.at = d.acctype;
-    L.sid = A.sid;
-    L.state = A.state;
-    L.tab = tab;
-    L.lp = lp;
-    L.err = &cnt[SEG_C_ERR];
-    L.grid = launch_grid(n, per_block, max_grid);
-    L.mask = mask;
-    L.level = rcl ? 1 : rul ? 2 : 0;
-    CR(locktab_seed(lt, L));
-  }
-  if (prof) CK(hipEventRecord(pev[1], stream));
-
-  // ---- rounds (seg_rounds.h's loop): decide(r) reads its list length `left`
-  // and appends the blocked txns to the list whose length word publish(r)
-  // cleared (the whole ring is clear before round 1, which takes every txn and
-  // clears nothing).  Rounds past the fixed point find empty lists.  `bound`
-  // sizes the grids.
-  // Key-sharded, the state bytes and so the ring are the same on every rank:
-  // every rank enqueues the same rounds, the ones past the fixed point too,
-  // and each of them makes its one exchange.
-  uint32_t rounds = 0;
-  if (sh) {
-    CR(rounds_loop(this, ring, n, n + 2, "nowait", rounds,
-                   [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) -> int {
-                     const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;
-                     const uint32_t tag = round_tag(er);
-                     const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
-                     const unsigned grid = launch_grid(bound, per_block, max_grid);
-                     if (r > 1) {
-                       if (er == 1) k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
-                       k_nw_publish<true><<<grid, NW_T, 0, stream>>>(AS, tag, lin, left, left_out);
-                     }
-                     k_nw_decide<NW_EVAL><<<grid, NW_T, 0, stream>>>(AS, tag, lin, left, nullptr, nullptr);
-                     CR(comm_allreduce_max_u8(AS.stat, n));
-                     k_nw_decide<NW_APPLY><<<grid, NW_T, 0, stream>>>(AS, tag, lin, left, lists[(r + 1) & 1], left_out);
-                     return DCC_OK;
-                   }));
-    k_nw_final<true><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(AS, rc_dev, conf_dev);
-    if (conf_dev) {  // the lowest conflicting ordinal over the ranks
-      CR(comm_allreduce_max_u8(AS.stat, n));
-      k_nw_conf<<<launch_grid(n, NW_T * 4, max_grid), NW_T, 0, stream>>>(n, A.state, AS.stat, conf_dev, cnt);
-    }
-  } else if (rul) {  // no rounds: one pass against the held rows
-    if (prof) CK(hipEventRecord(pev[2], stream));
-    k_nw_ru<<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
-    if (prof) CK(hipEventRecord(pev[3], stream));
-  } else if (rcl) {  // one more round than SERIALIZABLE at most: the words of the self-aborted txns
-    CR(rounds_loop(this, ring, n, n + 3, "nowait", rounds,
-                   [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
-                     const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;
-                     const uint32_t tag = round_tag(er);
-                     const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
-                     const unsigned grid = launch_grid(bound, per_block, max_grid);
-                     if (r > 1) {
-                       if (er == 1) k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
-                       k_nw_publish<false, ISO_RC><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, left_out);
-                     }
-                     k_nw_decide<NW_ONE, ISO_RC>
-                         <<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
-                   }));
-    k_nw_final<false, ISO_RC><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
-  } else {
-    CR(rounds_loop(this, ring, n, n + 2, "nowait", rounds,
-                   [&](uint32_t r, const uint32_t* left, uint32_t* left_out, uint64_t bound) {
-                     const uint32_t er = (r - 1) % MAX_TAG_ROUND + 1;  // tags 62 .. 1, then again
-                     const uint32_t tag = round_tag(er);
-                     const uint32_t* lin = r > 1 ? lists[r & 1] : nullptr;
-                     const unsigned grid = launch_grid(bound, per_block, max_grid);
-                     if (r > 1) {
-                       if (er == 1)  // tag space exhausted: drop the tagged words, every undecided txn republishes
-                         k_nw_retag<<<launch_grid(cap, NW_T * 4, max_grid), NW_T, 0, stream>>>(tab, cap);
-                       k_nw_publish<false><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, left_out);
-                     }
-                     k_nw_decide<NW_ONE><<<grid, NW_T, 0, stream>>>(A, tag, lin, left, lists[(r + 1) & 1], left_out);
-                   }));
-    k_nw_final<false><<<launch_grid(n, per_block, max_grid), NW_T, 0, stream>>>(A, rc_dev, conf_dev);
-  }
-  CK(hipGetLastError());
-  if (lt) CR(locktab_grant(lt, L));  // the committed txns' requests stay in the table
-  if (prof) CK(hipEventRecord(pev[4], stream));
-  CK(hipEventRecord(ev1, stream));
-  if (!dev) {
-    CK(hipMemcpyAsync(out_rc, rc_dev, n, hipMemcpyDeviceToHost, stream));
-    if (out_conflict) CK(hipMemcpyAsync(out_conflict, conf_dev, n * 4, hipMemcpyDeviceToHost, stream));
-  }
-  CK(hipMemcpyAsync(hmisc, cnt, NW_C_RING * 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  const uint32_t* hc = (const uint32_t*)hmisc;
-  if (hc[SEG_C_ERR] & CHK_ERR_KEY) return fail(DCC_EINVAL, "nowait: held key equal to DCC_KEY_RESERVED");
-  if (hc[SEG_C_ERR] & NW_ERR_FULL) return fail(DCC_EIO, "nowait: lock table full");
-  if (hc[SEG_C_ERR] & NW_ERR_STATE) return fail(DCC_EIO, "nowait: inconsistent decisions");
-  S.rounds = rounds;
-  S.n_commit = hc[NW_C_COMMIT];
-  S.n_abort = n - hc[NW_C_COMMIT];
-  S.nnz_w = hc[NW_C_NEX];
-  S.n_readonly = hc[NW_C_RO];
-  S.alg_bytes = dcc_nowait_iso_alg_bytes(n, m, hn, out_conflict != nullptr, iso);
-  if (lt) {
-    uint64_t granted = 0;
-    CR(locktab_end(lt, &granted));
-    S.alg_bytes = dcc_locktab_epoch_alg_bytes(n, m, granted, out_conflict != nullptr);
-  }
-  CR(es.finish(this, 4));
-  if (st) *st = S;
+  CR(stage_batch(b, R.d));
+  R.n = R.d.n;
+  R.m = R.d.nnz;
+  if (R.P.tab == NW_TAB_EARLY) CR(nw_table(this, R, nw_rows(R.P, R.m, nullptr)));
+  CR(nw_check(this, R, held, out_rc, out_conflict));
+  if (R.P.tab == NW_TAB_LATE) CR(nw_table(this, R, nw_rows(R.P, R.m, (const uint32_t*)hmisc)));
+  CR(nw_build(this, R, lt));
+  CR(nw_decide(this, R));
+  CR(nw_readout(this, R, lt, out_rc, out_conflict, es));
+  if (st) *st = es.S;
   return DCC_OK;
 }
 
@@ -941,6 +1007,8 @@ extern "C" int dcc_nowait_lock_epoch(dcc_ctx* ctx, const dcc_batch* batch, const
   if (!ctx || !batch || !out_rc) return DCC_EINVAL;
   dcc_pipe_drain(ctx);  // pipelined OCC epochs in flight complete first
   if (ctx->multi && (batch->flags & DCC_SHARD_SELF) && dcc_multi_size(ctx) > 1) {  // key-sharded over the ranks
+    // nw_plan's rejection, kept here too: it comes before dcc_multi_nowait_epoch's own checks and
+    // its empty-batch exit, and answers both isolation bits with DCC_ENOTSUP (one context: DCC_EINVAL)
     if (batch->flags & (DCC_ISO_READ_COMMITTED | DCC_ISO_READ_UNCOMMITTED))
       return ctx->fail(DCC_ENOTSUP, "nowait: a key-sharded epoch is SERIALIZABLE only");
     return dcc_multi_nowait_epoch(ctx, batch, held, out_rc, out_conflict, out_stats);

@@ -14,6 +14,8 @@ namespace dcc {
 constexpr uint32_t NW_T = 256;  // threads per workgroup
 // the epoch's error word (next to CHK_ERR_*): the per-epoch table is full
 constexpr uint32_t NW_ERR_FULL = 4;
+// the level of an epoch (DCC_ISO_*): LtEpoch::level, a template parameter of the rounds' kernels
+constexpr int ISO_SER = 0, ISO_RC = 1, ISO_RU = 2;
 
 __device__ inline uint32_t is_ex(uint8_t t) { return (t == DCC_RD || t == DCC_SCAN) ? 0u : 1u; }
 

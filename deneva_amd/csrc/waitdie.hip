@@ -597,6 +597,59 @@ int wd_checked(dcc_ctx* ctx, const uint32_t* hc, uint64_t n, uint64_t m, bool re
   return DCC_OK;
 }
 
+// What a lock epoch and a release share up to ev0: the call's arguments
+// checked, the batch and the state arrays on the device, the check, the key
+// pack and the lanes' geometry.  A.n == 0 behind a DCC_OK: the empty batch.
+struct WdOpen {
+  uint64_t per_block = 0, tiles = 0;
+  bool dev = false;
+  const uint8_t* leave_dev = nullptr;
+  unsigned max_grid = 1;
+  WdChecked c;
+  KeyPack kp{};
+  WdArgs A{};  // rc, pos, cnt: the state and the counters on the device
+};
+int wd_open(dcc_ctx* ctx, const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_io, uint32_t* pos_io, bool release,
+            const uint8_t* leave_in, uint64_t* out_left, uint64_t* out_promoted, WdOpen& O) {
+  hipStream_t stream = ctx->stream;
+  if (!ts_in || !rc_io || !pos_io) return ctx->fail(DCC_EINVAL, "waitdie: null ts / rc / pos");
+  if (release && !leave_in) return ctx->fail(DCC_EINVAL, "waitdie: null leave");
+  CR(ctx->check_batch(b, false));  // the offsets are checked on the device (k_wd_check)
+  if (ctx->comm_ranks() > 1) return ctx->fail(DCC_ENOTSUP, "waitdie: single-GPU engine");
+  O.dev = (b->flags & DCC_DEVICE_PTRS) != 0;
+  if (out_left) *out_left = 0;
+  if (out_promoted) *out_promoted = 0;
+  if (b->n_txn == 0) return DCC_OK;
+  DevBatch d;
+  CR(ctx->stage_batch(b, d));
+  const uint64_t n = d.n, m = d.nnz;
+  CR(ctx->waitdie_reserve(n, m, !O.dev));
+  const uint64_t* ts_dev;
+  uint8_t* rc_dev;
+  uint32_t* pos_dev;
+  CR(ctx->waitdie_stage(n, O.dev, ts_in, rc_io, pos_io, leave_in, ts_dev, rc_dev, pos_dev, O.leave_dev));
+  SegWork& W = ctx->seg;
+  uint32_t* cnt = (uint32_t*)W.misc.p;
+  O.max_grid = (unsigned)ctx->n_cu * 16;
+
+  // reject a malformed batch or state before anything indexes with it: rc,
+  // pos and the outputs are untouched by a rejected call
+  CK(hipMemsetAsync(cnt, 0, WD_C_WORDS * 4, stream));
+  k_wd_check<<<launch_grid(std::max(n, m), WD_T * 4, O.max_grid), WD_T, 0, stream>>>(
+      d.off, n, d.keys, m, ts_dev, rc_dev, pos_dev, O.leave_dev, cnt);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(ctx->hmisc, cnt, WD_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
+  CK(hipStreamSynchronize(stream));
+  CR(wd_checked(ctx, (const uint32_t*)ctx->hmisc, n, m, release, O.c));
+  O.kp = make_keypack(O.c.varying);
+  if (O.kp.bits > 63) return ctx->fail(DCC_ENOTSUP, "waitdie: the keys vary in all 64 bits");
+  O.per_block = WD_T >> O.c.lp;
+  O.tiles = (m + WD_TILE - 1) / WD_TILE;
+  O.A = WdArgs{n,      m,  d.off, d.keys, d.acctype, ts_dev, rc_dev, pos_dev,
+               O.c.lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p, (uint8_t*)ctx->wd_flg.p, cnt};
+  return DCC_OK;
+}
+
 }  // namespace
 
 int dcc_ctx::waitdie_reserve(uint64_t n, uint64_t nnz, bool host_arrays) {
@@ -642,52 +695,26 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   dcc_ctx* ctx = this;
   EpochStats es;
   dcc_stats& S = es.S;
-  if (!ts_in || !rc_io || !pos_io) return fail(DCC_EINVAL, "waitdie: null ts / rc / pos");
-  CR(check_batch(b, false));  // the offsets are checked on the device (k_wd_check)
-  if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "waitdie: single-GPU engine");
-  const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
-  if (b->n_txn == 0) {
+  WdOpen O;
+  CR(wd_open(this, b, ts_in, rc_io, pos_io, false, nullptr, nullptr, nullptr, O));
+  if (O.A.n == 0) {
     if (st) *st = S;
     return DCC_OK;
   }
-  DevBatch d;
-  CR(stage_batch(b, d));
-  const uint64_t n = d.n, m = d.nnz;
-  CR(waitdie_reserve(n, m, !dev));
-  const uint64_t* ts_dev;
-  uint8_t* rc_dev;
-  uint32_t* pos_dev;
-  const uint8_t* none;
-  CR(waitdie_stage(n, dev, ts_in, rc_io, pos_io, nullptr, ts_dev, rc_dev, pos_dev, none));
+  const uint64_t n = O.A.n, m = O.A.m, tiles = O.tiles;
+  const bool dev = O.dev, prof = profiling;
+  const unsigned max_grid = O.max_grid;
+  const KeyPack kp = O.kp;
+  const WdArgs& A = O.A;
   uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)wd_conf.p) : nullptr;
   SegWork& W = seg;
-  uint32_t* cnt = (uint32_t*)W.misc.p;
-  uint32_t* ring = cnt + WD_C_RING;
-  const unsigned max_grid = (unsigned)n_cu * 16;
-  const bool prof = profiling;
-
-  // reject a malformed batch or state before anything indexes with it: rc,
-  // pos and the outputs are untouched by a rejected call
-  CK(hipMemsetAsync(cnt, 0, WD_C_WORDS * 4, stream));
-  k_wd_check<<<launch_grid(std::max(n, m), WD_T * 4, max_grid), WD_T, 0, stream>>>(
-      d.off, n, d.keys, m, ts_dev, rc_dev, pos_dev, nullptr, cnt);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(hmisc, cnt, WD_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  WdChecked c;
-  CR(wd_checked(this, (const uint32_t*)hmisc, n, m, false, c));
-  const KeyPack kp = make_keypack(c.varying);
-  if (kp.bits > 63) return fail(DCC_ENOTSUP, "waitdie: the keys vary in all 64 bits");
-  const uint32_t lp = c.lp;
-  const uint64_t per_block = WD_T >> lp, tiles = (m + WD_TILE - 1) / WD_TILE;
+  uint32_t* cnt = A.cnt;
 
   CK(hipEventRecord(ev0, stream));
   if (prof) CK(hipEventRecord(pev[0], stream));
-  const WdArgs A{n,  m,  d.off, d.keys, d.acctype, ts_dev, rc_dev, pos_dev,
-                 lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p, (uint8_t*)wd_flg.p, cnt};
   uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
   uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
-  const unsigned agrid = launch_grid(n, per_block, max_grid);
+  const unsigned agrid = launch_grid(n, O.per_block, max_grid);
   k_wd_prep<<<agrid, WD_T, 0, stream>>>(A, kp, kb[0], vb[0]);
   CK(hipGetLastError());
   WdScan SA{};
@@ -707,7 +734,7 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   // which clears the ring word the round counts into / apply / advance.  The
   // lowest undecided txn is decided or moves its progress in every round.
   uint32_t rounds = 0;
-  CR(rounds_loop(this, ring, n, n + m + 2, "waitdie", rounds,
+  CR(rounds_loop(this, cnt + WD_C_RING, n, n + m + 2, "waitdie", rounds,
                  [&](uint32_t, const uint32_t* left, uint32_t* left_out, uint64_t) {
                    if (m) {
                      SA.left = left;
@@ -722,7 +749,7 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
 
   // rc / pos of a host call stay as they were unless the decisions are sound:
   // the final pass writes the staged copies
-  k_wd_final<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, A.stp, rc_dev, pos_dev, conf_dev, cnt);
+  k_wd_final<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, A.stp, A.rc, A.pos, conf_dev, cnt);
   CK(hipGetLastError());
   if (prof) CK(hipEventRecord(pev[4], stream));
   CK(hipEventRecord(ev1, stream));
@@ -737,8 +764,8 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   S.nnz_w = hc[WD_C_NEX];
   S.n_readonly = hc[WD_C_RO];
   if (!dev) {
-    CK(hipMemcpyAsync(rc_io, rc_dev, n, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(pos_io, pos_dev, n * 4, hipMemcpyDeviceToHost, stream));
+    CK(hipMemcpyAsync(rc_io, A.rc, n, hipMemcpyDeviceToHost, stream));
+    CK(hipMemcpyAsync(pos_io, A.pos, n * 4, hipMemcpyDeviceToHost, stream));
     if (out_conflict) CK(hipMemcpyAsync(out_conflict, conf_dev, n * 4, hipMemcpyDeviceToHost, stream));
     CK(hipStreamSynchronize(stream));
   }
@@ -754,46 +781,19 @@ int dcc_ctx::waitdie_release(const dcc_batch* b, const uint64_t* ts_in, uint8_t*
   dcc_ctx* ctx = this;
   EpochStats es;
   dcc_stats& S = es.S;
-  if (!ts_in || !rc_io || !pos_io) return fail(DCC_EINVAL, "waitdie: null ts / rc / pos");
-  if (!leave_in) return fail(DCC_EINVAL, "waitdie: null leave");
-  CR(check_batch(b, false));
-  if (comm_ranks() > 1) return fail(DCC_ENOTSUP, "waitdie: single-GPU engine");
-  const bool dev = (b->flags & DCC_DEVICE_PTRS) != 0;
-  if (out_left) *out_left = 0;
-  if (out_promoted) *out_promoted = 0;
-  if (b->n_txn == 0) {
+  WdOpen O;
+  CR(wd_open(this, b, ts_in, rc_io, pos_io, true, leave_in, out_left, out_promoted, O));
+  if (O.A.n == 0) {
     if (st) *st = S;
     return DCC_OK;
   }
-  DevBatch d;
-  CR(stage_batch(b, d));
-  const uint64_t n = d.n, m = d.nnz;
-  CR(waitdie_reserve(n, m, !dev));
-  const uint64_t* ts_dev;
-  uint8_t* rc_dev;
-  uint32_t* pos_dev;
-  const uint8_t* leave_dev;
-  CR(waitdie_stage(n, dev, ts_in, rc_io, pos_io, leave_in, ts_dev, rc_dev, pos_dev, leave_dev));
+  const uint64_t n = O.A.n, m = O.A.m, tiles = O.tiles;
+  const unsigned max_grid = O.max_grid;
+  const KeyPack kp = O.kp, tp = make_keypack(O.c.tvar);
+  const WdArgs& A = O.A;
   SegWork& W = seg;
-  uint32_t* cnt = (uint32_t*)W.misc.p;
-  const unsigned max_grid = (unsigned)n_cu * 16;
-
-  CK(hipMemsetAsync(cnt, 0, WD_C_WORDS * 4, stream));
-  k_wd_check<<<launch_grid(std::max(n, m), WD_T * 4, max_grid), WD_T, 0, stream>>>(
-      d.off, n, d.keys, m, ts_dev, rc_dev, pos_dev, leave_dev, cnt);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(hmisc, cnt, WD_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  WdChecked c;
-  CR(wd_checked(this, (const uint32_t*)hmisc, n, m, true, c));
-  const KeyPack kp = make_keypack(c.varying), tp = make_keypack(c.tvar);
-  if (kp.bits > 63) return fail(DCC_ENOTSUP, "waitdie: the keys vary in all 64 bits");
-  const uint32_t lp = c.lp;
-  const uint64_t per_block = WD_T >> lp, tiles = (m + WD_TILE - 1) / WD_TILE;
 
   CK(hipEventRecord(ev0, stream));
-  const WdArgs A{n,  m,  d.off, d.keys, d.acctype, ts_dev, rc_dev, pos_dev,
-                 lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p, (uint8_t*)wd_flg.p, cnt};
   if (m) {
     uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
     uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
@@ -801,35 +801,35 @@ int dcc_ctx::waitdie_release(const dcc_batch* b, const uint64_t* ts_in, uint8_t*
     // the records hold what the passes below need of rc / pos / leave: the
     // state is only written behind them (the checked offsets cover every
     // access, so k_wd_rprep writes every key and record)
-    k_wd_rprep<<<launch_grid(n, per_block, max_grid), WD_T, 0, stream>>>(A, leave_dev, tp, kb[0], vb[0]);
+    k_wd_rprep<<<launch_grid(n, O.per_block, max_grid), WD_T, 0, stream>>>(A, O.leave_dev, tp, kb[0], vb[0]);
     CK(hipGetLastError());
     const int c1 = radix_sort_u64(kb, vb, m, tp.bits, (uint32_t*)cv_scratch.p, stream);
     uint64_t* kb2[2] = {kb[c1], kb[c1 ^ 1]};
     uint32_t* vb2[2] = {vb[c1], vb[c1 ^ 1]};
-    k_wd_rkey<<<mgrid, WD_T, 0, stream>>>(m, A.arec, d.keys, kp, vb2[0], kb2[0]);
+    k_wd_rkey<<<mgrid, WD_T, 0, stream>>>(m, A.arec, A.keys, kp, vb2[0], kb2[0]);
     CK(hipGetLastError());
     const int c2 = radix_sort_u64(kb2, vb2, m, kp.bits + 1, (uint32_t*)cv_scratch.p, stream);
     k_wd_rseg<<<mgrid, WD_T, 0, stream>>>(m, A.arec, kb2[c2], vb2[c2], (uint32_t*)W.stxn.p,
                                           (uint32_t*)W.sinfo.p);
     CK(hipGetLastError());
     const WdRel R{m,       (const uint32_t*)W.stxn.p, (const uint32_t*)W.sinfo.p, (uint64_t*)W.agg.p,
-                  (uint64_t*)W.agg.p + tiles, rc_dev, pos_dev,                     cnt};
+                  (uint64_t*)W.agg.p + tiles, A.rc,   A.pos,                       A.cnt};
     k_wd_rscan<false><<<(unsigned)tiles, WD_T, 0, stream>>>(R);
     k_tile_aggscan<RqOp><<<1, SEG_AGG_T, 0, stream>>>(R.agg, R.pre, tiles, nullptr, nullptr);
     k_wd_rscan<true><<<(unsigned)tiles, WD_T, 0, stream>>>(R);
     CK(hipGetLastError());
   }
-  k_wd_rgone<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, leave_dev, rc_dev);
+  k_wd_rgone<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, O.leave_dev, A.rc);
   CK(hipGetLastError());
   CK(hipEventRecord(ev1, stream));
-  CK(hipMemcpyAsync(hmisc, cnt, WD_C_RING * 4, hipMemcpyDeviceToHost, stream));
-  if (!dev) {
-    CK(hipMemcpyAsync(rc_io, rc_dev, n, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(pos_io, pos_dev, n * 4, hipMemcpyDeviceToHost, stream));
+  CK(hipMemcpyAsync(hmisc, A.cnt, WD_C_RING * 4, hipMemcpyDeviceToHost, stream));
+  if (!O.dev) {
+    CK(hipMemcpyAsync(rc_io, A.rc, n, hipMemcpyDeviceToHost, stream));
+    CK(hipMemcpyAsync(pos_io, A.pos, n * 4, hipMemcpyDeviceToHost, stream));
   }
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
-  S.n_commit = c.count;
+  S.n_commit = O.c.count;
   S.n_survivors = hc[WD_C_PROM];
   if (out_left) *out_left = S.n_commit;
   if (out_promoted) *out_promoted = S.n_survivors;
