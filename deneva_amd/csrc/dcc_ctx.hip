@@ -145,6 +145,10 @@ extern "C" int dcc_init(dcc_ctx** out, int device_id) {
   CK(hipHostGetDevicePointer(&ctx->hmisc_dev, ctx->hmisc, 0));
   CK(hipHostGetDevicePointer(&ctx->hpart_dev, ctx->hpart, 0));
   ctx->hs[1].chained = true;  // the delta level (dcc_ctx.h HistStore)
+  // ... which has no table yet: its first build makes the empty one that the
+  // first epoch's appends are pushed into (else they would join the flat
+  // pairs only and no window would ever find them)
+  ctx->hs[1].built = false;
   CK(hipHostMalloc((void**)&ctx->hdyn, dcc_ctx::HDYN_BYTES, hipHostMallocDefault));
   CK(hipHostGetDevicePointer(&ctx->hdyn_dev, ctx->hdyn, 0));
   memset(ctx->hdyn, 0, dcc_ctx::HDYN_BYTES);

@@ -83,11 +83,11 @@ __global__ __launch_bounds__(256) void k_ix_probe(const uint64_t* keys, uint64_t
     uint64_t s = ix_hash(key, bits);
     for (uint64_t q = 0; q <= mask; q++, s = (s + 1) & mask) {
       const uint64_t v = tk[s];
+      if (v == DCC_KEY_RESERVED) break;  // empty first: the reserved key itself is never found
       if (v == key) {
         r = rows[tord[s]];
         break;
       }
-      if (v == DCC_KEY_RESERVED) break;
     }
     miss += r == DCC_ROW_NONE;
     out[i] = r;
@@ -186,6 +186,9 @@ extern "C" int dcc_index_insert(dcc_ctx* ctx, const uint64_t* keys, const uint64
   if (!ctx || (n && (!keys || !rows))) return DCC_EINVAL;
   if (ctx->multi) return ctx->fail(DCC_ENOTSUP, "index: single-GPU");
   if (n == 0) return DCC_OK;
+  // rejected before anything changes: the table, its size and the ordinals stay
+  for (uint64_t i = 0; i < n; i++)
+    if (keys[i] == DCC_KEY_RESERVED) return ctx->fail(DCC_EINVAL, "index: key equal to DCC_KEY_RESERVED");
   if (hipSetDevice(ctx->device) != hipSuccess) return DCC_ENODEV;
   CR(ctx->index_reserve(ctx->ix_nkeys + n));
   // the rows of every insert so far, by ordinal (grow-with-copy)
@@ -320,6 +323,8 @@ extern "C" int dcc_calvin_dispatch(dcc_ctx* ctx, const uint32_t* wave, const uin
   uint32_t hmx = 0;
   CK(hipMemcpyAsync(&hmx, mx, 4, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
+  // max wave + 1 must fit *out_n_waves (and the offsets loop of k_wv_off ends at it)
+  if (hmx == 0xFFFFFFFFu) return ctx->fail(DCC_ERANGE, "dispatch: wave level 2^32-1");
   const uint32_t nw = hmx + 1;
   *out_n_waves = nw;
   if (out_wave_off && off_cap < (uint64_t)nw + 1)

@@ -1128,7 +1128,8 @@ uint64_t dcc_abortq_pop_alg_bytes(uint64_t n_q, uint64_t nnz_q, uint64_t n_due, 
  * released its locks (TxnTable::restart_txn, txn_table.cpp:151-176, after the
  * lock_release promotions of row_lock.cpp:317-357).  *out_n_waves = max
  * wave + 1; out_wave_off needs *out_n_waves + 1 entries (off_cap; may be NULL
- * to query the count).  Device pointers with DCC_DEVICE_PTRS in flags. */
+ * to query the count).  A wave level of 2^32-1 (the count would not fit) is
+ * DCC_ERANGE.  Device pointers with DCC_DEVICE_PTRS in flags. */
 int dcc_calvin_dispatch(dcc_ctx* ctx, const uint32_t* wave, const uint64_t* order, uint64_t n,
                         uint32_t flags, uint32_t* out_wave_off, uint64_t off_cap,
                         uint32_t* out_txn, uint32_t* out_n_waves);
@@ -1141,8 +1142,13 @@ int dcc_calvin_dispatch(dcc_ctx* ctx, const uint32_t* wave, const uint64_t* orde
  * missing key (the reference's M_ASSERT_V, index_hash.cpp:221) reads as
  * DCC_ROW_NONE and is counted in *out_missing. */
 #define DCC_ROW_NONE 0xFFFFFFFFFFFFFFFFull
+/* keys / rows: host arrays.  A key equal to DCC_KEY_RESERVED rejects the
+ * whole call with DCC_EINVAL before anything changes: none of its keys is
+ * inserted and dcc_index_size stays. */
 int dcc_index_insert(dcc_ctx* ctx, const uint64_t* keys, const uint64_t* rows, uint64_t n);
-/* keys / out_rows: host arrays, or device arrays with DCC_DEVICE_PTRS in flags */
+/* keys / out_rows: host arrays, or device arrays with DCC_DEVICE_PTRS in
+ * flags.  DCC_KEY_RESERVED is never in the index: it reads as DCC_ROW_NONE
+ * and counts as missing. */
 int dcc_index_probe(dcc_ctx* ctx, const uint64_t* keys, uint64_t n, uint64_t* out_rows,
                     uint32_t flags, uint64_t* out_missing);
 int dcc_index_clear(dcc_ctx* ctx);

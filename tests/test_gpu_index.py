@@ -10,17 +10,9 @@ import pytest
 import _oracle as orc
 import deneva_amd as d
 from deneva_amd._abi import ROW_NONE
+from index_ref import index_oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def index_oracle(inserts, probe):
-    """BucketHeader::insert_item / read_item: the newest item of a key."""
-    m = {}
-    for keys, rows in inserts:
-        for k, r in zip(keys.tolist(), rows.tolist()):
-            m[k] = r
-    return np.array([m.get(k, ROW_NONE) for k in probe.tolist()], np.uint64)
 
 
 def test_index_build_probe_duplicates_growth():
