@@ -567,6 +567,15 @@ struct dcc_ctx {
   // exchange, then 64 - the conflict ordinal); a multi-GPU context's per-rank
   // conflict ordinals of a device batch
   DevBuf nw_stat, sh_conf;
+  // MVCC with txns in flight (mvcc_live.hip).  The state is the caller's (rc,
+  // pos) arrays, rows and versions are the MVCC epoch's above; the workspaces
+  // are `seg`, the WAIT_DIE calls' flag bytes and host staging, the TIMESTAMP
+  // epoch's head slots and the MVCC epoch's version lists
+  int mvcc_live_reserve(uint64_t n, uint64_t nnz, bool host_arrays);
+  int mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, uint64_t* vts,
+                        uint32_t* out_conflict, dcc_stats* st);
+  int mvcc_finish(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
+                  uint64_t* vts, uint64_t* out_left, uint64_t* out_promoted, dcc_stats* st);
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes

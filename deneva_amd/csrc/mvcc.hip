@@ -68,13 +68,14 @@ constexpr uint32_t TS_ITEMS = 4;                  // consecutive sorted accesses
 }  // namespace
 }  // namespace dcc
 
+#include "mvcc_store.h"
 #include "tso_kernels.h"
 
 namespace {
 
 // engine counter words (next to tso_kernels.h's): late accesses; the epoch's versions (u64)
 constexpr uint32_t MV_C_NLATE = TS_C_ENGINE, MV_C_NC = TS_C_ENGINE + 2;
-constexpr uint32_t MV_OFF_T = 1024;  // threads of the tile-offset scan
+static_assert(TS_T == MVS_T, "the store kernels' workgroup");
 
 struct MvScanArgs : ScanArgs {
   uint64_t* vts;     // [m] the version of every access, batch order (null: not wanted)
@@ -180,41 +181,7 @@ __global__ __launch_bounds__(TS_T) void k_mv_commits(uint64_t m, const uint32_t*
     }
 }
 
-// Exclusive scan of the tile counts in place, one workgroup; the sum to *total.
-__global__ __launch_bounds__(MV_OFF_T) void k_mv_offsets(uint64_t* toff, uint64_t tiles, uint64_t* total) {
-  __shared__ uint64_t s_w[MV_OFF_T / 64];
-  uint64_t carry = 0;
-  for (uint64_t c0 = 0; c0 < tiles; c0 += MV_OFF_T) {
-    const uint64_t i = c0 + threadIdx.x;
-    const uint64_t v = i < tiles ? toff[i] : 0;
-    uint64_t sum;
-    const uint64_t ex = block_excl_reuse<MV_OFF_T / 64, AddOp<uint64_t>>(v, s_w, sum);
-    if (i < tiles) toff[i] = carry + ex;
-    carry += sum;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
 // ------------------------------------------------------------- late lookup
-// The number of leading elements of (k[], t[]) with (key, ts) <= (K, T).
-__device__ inline uint64_t mv_upper(const uint64_t* __restrict__ k, const uint64_t* __restrict__ t, uint64_t n,
-                                    uint64_t K, uint64_t T) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    const uint64_t kk = k[mid];
-    if (kk < K || (kk == K && t[mid] <= T)) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-struct MvStore {
-  const uint64_t* k;
-  const uint64_t* t;
-  uint64_t n;
-};
-
 __global__ __launch_bounds__(TS_T) void k_mv_lookup(const uint32_t* __restrict__ late,
                                                     const uint32_t* __restrict__ nlate,
                                                     const uint64_t* __restrict__ keys,
@@ -248,36 +215,6 @@ __global__ __launch_bounds__(TS_T) void k_mv_lookup(const uint32_t* __restrict__
       if (p && S.k[p - 1] == K) v = S.t[p - 1];
     }
     vts[x] = v;
-  }
-}
-
-// -------------------------------------------------------------------- store
-// Merge by rank into (dk, dt): old element i goes to i + the new elements with
-// a smaller key, new element j to j + the old elements with a key <= its own.
-// (Within a key every old ts <= every new one, so this is (key, ts) order.)
-__global__ __launch_bounds__(TS_T) void k_mv_merge(MvStore S, const uint64_t* __restrict__ ek,
-                                                   const uint64_t* __restrict__ et,
-                                                   const uint64_t* __restrict__ nc_p, uint64_t* __restrict__ dk,
-                                                   uint64_t* __restrict__ dt) {
-  const uint64_t nc = *nc_p, all = S.n + nc;
-  for (uint64_t g = (uint64_t)blockIdx.x * TS_T + threadIdx.x; g < all; g += (uint64_t)gridDim.x * TS_T) {
-    uint64_t k, t, pos;
-    if (g < S.n) {
-      k = S.k[g], t = S.t[g];
-      uint64_t lo = 0, hi = nc;  // new elements with key < k
-      while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (ek[mid] < k) lo = mid + 1;
-        else hi = mid;
-      }
-      pos = g + lo;
-    } else {
-      const uint64_t j = g - S.n;
-      k = ek[j], t = et[j];
-      pos = j + mv_upper(S.k, S.t, S.n, k, ~0ull);
-    }
-    dk[pos] = k;
-    dt[pos] = t;
   }
 }
 
@@ -423,7 +360,7 @@ int dcc_ctx::mvcc_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* out_
     uint32_t* ex = (uint32_t*)mv_ex.p;
     k_mv_commits<false><<<(unsigned)tiles, TS_T, 0, stream>>>(m, SA.s_info, SA.s_txn, SA.s_ts, SA.sv, SA.stp,
                                                               d.keys, toff, ek, et, ex);
-    k_mv_offsets<<<1, MV_OFF_T, 0, stream>>>(toff, tiles, nc_dev);
+    k_mv_offsets<<<1, MVS_OFF_T, 0, stream>>>(toff, tiles, nc_dev);
     k_mv_commits<true><<<(unsigned)tiles, TS_T, 0, stream>>>(m, SA.s_info, SA.s_txn, SA.s_ts, SA.sv, SA.stp,
                                                              d.keys, toff, ek, et, ex);
     if (vts_dev)
@@ -480,7 +417,7 @@ int dcc_ctx::mvcc_trim(uint64_t floor, uint64_t* n_dropped) {
   uint64_t* dk = (uint64_t*)mv_sk[mv_cur ^ 1].p;
   uint64_t* dt = (uint64_t*)mv_st[mv_cur ^ 1].p;
   k_mv_trim<false><<<(unsigned)tiles, TS_T, 0, stream>>>(old, floor, toff, dk, dt);
-  k_mv_offsets<<<1, MV_OFF_T, 0, stream>>>(toff, tiles, toff + tiles);
+  k_mv_offsets<<<1, MVS_OFF_T, 0, stream>>>(toff, tiles, toff + tiles);
   k_mv_trim<true><<<(unsigned)tiles, TS_T, 0, stream>>>(old, floor, toff, dk, dt);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(hmisc, toff + tiles, 8, hipMemcpyDeviceToHost, stream));

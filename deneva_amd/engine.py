@@ -805,6 +805,61 @@ class Engine:
     def mvcc_clear(self) -> None:
         _check(lib.dcc_mvcc_clear(self._h), self._h)
 
+    # ------------------------------------------ MVCC with txns in flight
+    def _mvcc_vts(self, what, batch, vts):
+        """The caller-kept versions array of an MVCC call with txns in flight:
+        nnz 8-byte items of the batch's kind, updated in place."""
+        if vts is None:
+            return None
+        if batch.on_device:
+            if not _is_device(vts) or not vts.is_contiguous():
+                raise TypeError(f"{what}: a device batch takes a contiguous device vts tensor")
+        elif not (isinstance(vts, np.ndarray) and vts.dtype == np.uint64 and vts.flags["C_CONTIGUOUS"] and
+                  vts.flags["WRITEABLE"]):
+            raise TypeError(f"{what}: vts is updated in place: a writable contiguous uint64 array")
+        if _itemsize(vts) != 8 or vts.shape[0] < batch.nnz:
+            raise ValueError(f"{what}: vts must hold nnz 8-byte items")
+        return _ptr(vts) if vts.shape[0] else None
+
+    def mvcc_access_epoch(self, batch: EpochBatch, ts, rc, pos, vts=None, want_conflict: bool = True):
+        """MVCC epoch with txns in flight (dcc_mvcc_access_epoch): the WD_RUN
+        txns send their requests from pos on against the pending prewrites of
+        the state and the context's MVCC rows and versions.  rc, pos and vts
+        (the version every executed read returned, kept by the caller across
+        calls; None: not wanted) are updated in place.  Returns (rc[:n],
+        pos[:n], conflict u32[n] | None, stats); conflict[i] is the ordinal of
+        the access a txn waits or aborted at, ACCESS_NONE otherwise.  Arrays
+        are numpy for a host batch, device tensors for a device batch."""
+        n = batch.n_txn
+        keep, ptrs = self._waitdie_state("mvcc_access_epoch", batch, ts, rc, pos)
+        vp = self._mvcc_vts("mvcc_access_epoch", batch, vts)
+        conf = None
+        if want_conflict:
+            if batch.on_device:
+                import torch
+                conf = torch.empty(max(n, 1), dtype=torch.int32, device=batch.offsets.device)
+            else:
+                conf = np.empty(max(n, 1), np.uint32)
+        st = _abi.Stats()
+        b = batch.to_c()
+        _check(lib.dcc_mvcc_access_epoch(self._h, C.byref(b), *ptrs, vp, _ptr(conf), C.byref(st)), self._h)
+        return rc[:n], pos[:n], (conf[:n] if want_conflict else None), st.as_dict()
+
+    def mvcc_finish(self, batch: EpochBatch, ts, rc, pos, leave, vts=None):
+        """dcc_mvcc_finish: the txns with leave[i] != 0 commit (RC_RCOK) or
+        abort (RC_ABORT, WD_RUN) and become WD_GONE; buffered reads that no
+        remaining prewrite blocks are promoted to (WD_RUN, pos + 1) and their
+        version goes to vts.  rc, pos and vts are updated in place.  Returns
+        (n_left, n_promoted, stats)."""
+        keep, ptrs = self._waitdie_state("mvcc_finish", batch, ts, rc, pos, leave)
+        vp = self._mvcc_vts("mvcc_finish", batch, vts)
+        st = _abi.Stats()
+        b = batch.to_c()
+        left, prom = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.dcc_mvcc_finish(self._h, C.byref(b), *ptrs, vp, C.byref(left), C.byref(prom), C.byref(st)),
+               self._h)
+        return int(left.value), int(prom.value), st.as_dict()
+
     # ------------------------------------------- select by decision (carry)
     def select_batch(self, batch: EpochBatch, rc, want: int = _abi.RC_ABORT, src=None, out=None,
                      txn_base: int = 0, nnz_base: int = 0, want_src: bool = True):
@@ -1335,6 +1390,10 @@ def waitdie_carry_alg_bytes(n_txn: int, n_kept: int, nnz_kept: int, n_fresh: int
                             with_revive: bool = False, with_src: bool = True) -> int:
     return int(lib.dcc_waitdie_carry_alg_bytes(n_txn, n_kept, nnz_kept, n_fresh, nnz_fresh, int(with_revive),
                                                int(with_src)))
+
+
+def mvcc_access_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True, with_vts: bool = True) -> int:
+    return int(lib.dcc_mvcc_access_alg_bytes(n_txn, nnz, int(with_conflict), int(with_vts)))
 
 
 def mvcc_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True, with_vts: bool = True) -> int:

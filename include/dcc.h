@@ -667,6 +667,95 @@ int dcc_mvcc_clear(dcc_ctx* ctx);
  * counted. */
 uint64_t dcc_mvcc_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict, int with_vts);
 
+/* ------------------------------------------------ MVCC with txns in flight */
+/* Row_mvcc with its buffers (readreq_mvcc, prereq_mvcc; row_mvcc.cpp:95-171,
+ * :242-364) as two calls, the split of the WAIT_DIE calls below: an epoch that
+ * only sends requests -- it decides pass, wait or abort for every access and
+ * nothing finishes inside it -- and a finish the caller makes between epochs
+ * for the txns that are done, which installs versions, drops prewrites and
+ * promotes buffered reads as Row_mvcc::update_buffer does.  When other txns
+ * finish is thereby an input.  DESIGN.md §8r has the arguments.
+ *
+ * State.  The WAIT_DIE calls' (see there): caller-owned rc[n_txn] (u8),
+ * pos[n_txn] (u32) and ts[n_txn] over a batch the caller keeps, with the same
+ * five bytes DCC_WD_RUN, DCC_RC_RCOK, DCC_RC_WAIT, DCC_RC_ABORT, DCC_WD_GONE, so
+ * that dcc_waitdie_carry and dcc_batch_select move an MVCC population
+ * unchanged.  ts[i] of a txn that is not GONE is any u64 in [1, 2^64-2], in any
+ * order, ties allowed.  With len the txn's access count:
+ *   a txn that is not GONE holds one pending prewrite (ts[i]) on the row of
+ *   each of its WR accesses in [0, pos);
+ *   a WAIT txn (pos < len) has a buffered read on the row of access pos, and if
+ *   that access is a WR also that access's prewrite (P_REQ precedes R_REQ,
+ *   row.cpp:252-258);
+ *   a new txn is (RUN, 0); RCOK has pos == len.
+ * rts, the latest version and every version of each row are the context's MVCC
+ * rows and store above, shared with dcc_mvcc_validate_epoch, dcc_mvcc_rows_get,
+ * dcc_mvcc_versions_*, dcc_mvcc_trim and dcc_mvcc_clear.
+ * dcc_mvcc_validate_epoch ignores pending prewrites: calling it on a context
+ * while a population holds any is the caller's error.
+ * vts (may be NULL) is a caller-kept [nnz] array in batch order: each call
+ * writes the entries of the accesses whose R_REQ it executes (the version's
+ * timestamp, DCC_VTS_BASE for the base row) and leaves the others alone.
+ *
+ * dcc_mvcc_access_epoch.  The RUN txns run in index order, each from pos[i], in
+ * list order, against the state of all other txns, the prefixes the RUN txns
+ * hold and what the RUN txns before them did:
+ *   WR        P_REQ aborts iff ts < rts of the row; otherwise the prewrite
+ *             becomes pending and R_REQ follows;
+ *   RD/SCAN   R_REQ only; XP sends nothing;
+ *   R_REQ     waits iff some pending prewrite of the row is below ts (the txn's
+ *             own prewrites and ties never block); otherwise it returns the
+ *             largest version <= ts, or the base row, and rts = max(rts, ts).
+ * First abort: (ABORT, ordinal); first wait: (WAIT, ordinal), out_conflict[i]
+ * the ordinal in both; past the last access (RCOK, len), DCC_ACCESS_NONE.  Txns
+ * that are not RUN are unchanged, their out_conflict is DCC_ACCESS_NONE.
+ * Cleanup is deferred: an aborted txn keeps the prewrites it made, old and new,
+ * until a finish releases it, and its rts bumps stay, as in the reference,
+ * whose cleanup is not atomic with the abort decision.  The reference's caps
+ * g_max_read_req / g_max_pre_req (the txns in flight) are not modelled.
+ *
+ * dcc_mvcc_finish.  leave[i] != 0 marks the txns that go.  An RCOK leaver
+ * commits: W_REQ per WR access installs version ts.  An ABORT or RUN leaver
+ * aborts: XP_REQ per WR access in [0, pos).  A WAIT leaver is DCC_EINVAL
+ * (wait-for edges run from larger to smaller ts, so no txn waits for ever); a
+ * GONE one is ignored.  The leavers become GONE.  Then per row a buffered read
+ * with ts <= the least remaining pending prewrite ts is promoted
+ * (debuffer_req(R_REQ), :143-167): it reads the largest version <= ts of the
+ * store after the installs, raises rts, and (WAIT, p) becomes (RUN, p + 1); a
+ * RUN txn at pos == len turns RCOK in the next epoch.  This equals releasing
+ * the leavers one at a time in index order, newest access first.  *out_left
+ * (host, may be NULL) = the leavers that were not GONE, *out_promoted (host, may
+ * be NULL) = the promoted txns.
+ *
+ * rc / pos / vts are updated in place.  With DCC_DEVICE_PTRS every array is
+ * device memory, otherwise a host array.  Compact batch forms are accepted;
+ * start_tn / finish_tn / order are ignored.  DCC_EINVAL, with nothing written:
+ * malformed offsets, the reserved key, a txn longer than MAX_ROW_PER_TXN, NULL
+ * ts / rc / pos (leave for a finish), an rc byte outside the five states, pos >
+ * len, RCOK with pos != len, WAIT with pos >= len, a ts of 0 or UINT64_MAX of a
+ * txn that is not GONE, a WAIT leaver.  An epoch whose keys vary in all 64 bits
+ * is DCC_ENOTSUP (its sort needs one bit next to the row; the finish needs
+ * none).  One GPU: a dcc_init_multi context runs on rank 0; a communicator of
+ * more than one rank is DCC_ENOTSUP; pipelined OCC epochs in flight complete
+ * first.  A call that fails behind its decisions (DCC_EIO) leaves the rows'
+ * values and the store as they were.
+ * Stats of the epoch: n_commit / n_abort / n_survivors = the txns that became
+ * RCOK / ABORT / WAIT; nnz_w = WR requests (the WR accesses at or past pos of
+ * the RUN txns), n_readonly = RUN txns with none; rounds, device_ms, total_ms,
+ * alg_bytes; phase_ms as dcc_waitdie_lock_epoch.  Stats of the finish:
+ * n_commit = leavers, n_survivors = promoted, nnz_w = versions installed,
+ * device_ms, total_ms. */
+int dcc_mvcc_access_epoch(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
+                          uint64_t* vts /* [nnz], may be NULL */, uint32_t* out_conflict /* may be NULL */,
+                          dcc_stats* out_stats);
+int dcc_mvcc_finish(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
+                    const uint8_t* leave, uint64_t* vts /* may be NULL */, uint64_t* out_left,
+                    uint64_t* out_promoted /* host, may be NULL */, dcc_stats* out_stats);
+/* Algorithmic bytes of one access epoch: dcc_waitdie_alg_bytes (the 24-B row
+ * aggregate being rts, least pending prewrite, latest version) [+ 8 nnz
+ * versions out].  The store's traffic is not counted. */
+uint64_t dcc_mvcc_access_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict, int with_vts);
+
 /* -------------------------------------------------------------- WAIT_DIE */
 /* CC_ALG WAIT_DIE (Row_lock, concurrency_control/row_lock.cpp) as two calls:
  * an epoch that only acquires -- it decides grant, wait or die for every
