@@ -80,7 +80,7 @@ struct RowTab {
 // and the lock state are elsewhere.  The sharing depends on that.
 struct SegWork {
   static constexpr uint64_t TILE = 1024;    // accesses per scan tile (TS_TILE, WD_TILE)
-  static constexpr uint32_t C_WORDS = 84;   // counter words (>= TS_C_WORDS, WD_C_WORDS)
+  static constexpr uint32_t C_WORDS = 84;   // counter words (>= TS_C_WORDS, LV_C_WORDS)
   static constexpr size_t AGG_BYTES = 40;   // a tile aggregate (sizeof(Tq), sizeof(Wq))
   DevBuf misc;               // counters, the ring of undecided counts
   DevBuf stp;                // [n] txn words
@@ -543,21 +543,20 @@ struct dcc_ctx {
                  uint64_t* out_vts, dcc_stats* st);
   int mvcc_trim(uint64_t floor, uint64_t* n_dropped);
   int mvcc_export(uint64_t* keys, uint64_t* ts, uint64_t cap, uint64_t* n_out);
-  // WAIT_DIE (waitdie.hip).  The lock state is the caller's (rc, pos) arrays;
-  // next to `seg` these are workspaces only: the flag byte of every dynamic
-  // access; ts / rc / pos / leave and the conflict ordinals of a host call
-  DevBuf wd_flg;
-  DevBuf wd_hts, wd_hrc, wd_hpos, wd_hleave, wd_conf;
-  int waitdie_reserve(uint64_t n, uint64_t nnz, bool host_arrays);
-  int waitdie_stage(uint64_t n, bool dev, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
-                    const uint64_t*& ts_d, uint8_t*& rc_d, uint32_t*& pos_d, const uint8_t*& leave_d);
+  // the live-txn calls' workspaces next to `seg` (live_txn.h): flag bytes, a host call's state and conflicts
+  DevBuf lv_flg;
+  DevBuf lv_hts, lv_hrc, lv_hpos, lv_hleave, lv_conf;
+  int live_reserve(uint64_t n, uint64_t nnz, bool host_arrays);
+  int live_stage(uint64_t n, bool dev, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
+                 const uint64_t*& ts_d, uint8_t*& rc_d, uint32_t*& pos_d, const uint8_t*& leave_d);
+  // WAIT_DIE (waitdie.hip).  The lock state is the caller's (rc, pos) arrays
   int waitdie_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, uint32_t* out_conflict,
                     dcc_stats* st);
   int waitdie_release(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
                       uint64_t* out_left, uint64_t* out_promoted, dcc_stats* st);
   // the population's carry between two epochs (waitdie_carry.hip).  Control
   // words and tile pairs are the select's; of a host call the population's
-  // state goes through the staging above (revive through wd_hleave, src_in
+  // state goes through the staging above (revive through lv_hleave, src_in
   // through sel_src), the fresh batch and the outputs through these
   DevBuf wc_foff, wc_fkeys, wc_fat, wc_fts, wc_out;
   int carry_reserve(uint64_t n, uint64_t nnz);
@@ -569,8 +568,8 @@ struct dcc_ctx {
   DevBuf nw_stat, sh_conf;
   // MVCC with txns in flight (mvcc_live.hip).  The state is the caller's (rc,
   // pos) arrays, rows and versions are the MVCC epoch's above; the workspaces
-  // are `seg`, the WAIT_DIE calls' flag bytes and host staging, the TIMESTAMP
-  // epoch's head slots and the MVCC epoch's version lists
+  // are the live-txn calls', the TIMESTAMP epoch's head slots and the MVCC
+  // epoch's version lists
   int mvcc_live_reserve(uint64_t n, uint64_t nnz, bool host_arrays);
   int mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, uint64_t* vts,
                         uint32_t* out_conflict, dcc_stats* st);

@@ -52,18 +52,17 @@
 // out are written by the last two kernels, which return at once if the error
 // word is set; the host swaps the store's buffers only if it is clear.
 //
-// Kernels:  k_ml_check   offsets / keys / longest txn / the (rc, pos) state /
-//                        the timestamps' range and varying bits / WAIT leavers
-//           k_ml_prep    sort keys, access records, txn words, request counts
+// Kernels:  k_live_check / k_live_prep / k_live_advance / k_live_final /
+//           k_live_gone  live_txn.h's, with MlLive below: the
+//                        check, sort keys / records / txn words, one round of
+//                        decisions, rc / pos / conflict ordinals, the leavers
 //           k_ml_seg     sorted records, row heads and ends
 //           k_ts_seed    (tso_kernels.h) the rows' slots
 //           k_ml_scan    per 1,024-access tile: its aggregate, or behind the
 //                        scanned aggregates four bits per dynamic access;
 //                        final: versions and rts
-//           k_ml_advance one round of decisions
-//           k_ml_final   rc, pos, conflict ordinals, counts
-//           k_ml_fprep / k_ml_fkey / k_ml_inst / k_mv_merge / k_ml_fscan /
-//           k_ml_gone: the finish
+//           k_ml_fprep / k_ml_fkey / k_ml_inst / k_mv_merge / k_ml_fscan: the
+//           finish
 // No workgroup waits on another.
 #include <hip/hip_runtime.h>
 
@@ -79,30 +78,25 @@ constexpr uint32_t TS_ITEMS = 4;  // consecutive sorted accesses per thread
 }  // namespace
 }  // namespace dcc
 
+#include "live_txn.h"
 #include "mvcc_store.h"
 #include "tso_kernels.h"
 
 namespace {
 
 static_assert(TS_T == MVS_T, "the store kernels' workgroup");
-// error bits next to tso_kernels.h's
-constexpr uint32_t ML_ERR_RC = 32, ML_ERR_POS = 64, ML_ERR_LEAVE = 128;
-// counter words next to tso_kernels.h's (TS_C_NWR: WR requests, TS_C_RO: RUN
-// txns without one, TS_C_COMMIT: RCOK).  The finish has no ring and keeps its
-// own words there; TOR / TNOR are u64
-constexpr uint32_t ML_C_ABORT = 7, ML_C_NC = TS_C_ENGINE, ML_C_WAIT = 14, ML_C_LATE = 80;
-constexpr uint32_t ML_C_TOR = TS_C_RING, ML_C_TNOR = TS_C_RING + 2, ML_C_LEFT = TS_C_RING + 4,
-                   ML_C_NINST = TS_C_RING + 5, ML_C_PROM = TS_C_RING + 6;
+// live_txn.h's error bits and counter words next to what k_ts_seed and the
+// final scan leave in the same words; the engine's own: the versions installed
+// (u64), the versions to install, the late reads
+static_assert(LV_ERR_STATE == TS_ERR_STATE && LV_ERR_TS == TS_ERR_TS &&
+                  !(TS_ERR_FULL & (LV_ERR_STATE | LV_ERR_TS | LV_ERR_RC | LV_ERR_POS | LV_ERR_LEAVE)),
+              "the error bits of both headers in one word");
+constexpr uint32_t ML_C_NC = TS_C_ENGINE, ML_C_NINST = LV_C_ENGINE, ML_C_LATE = 80;
 constexpr uint32_t ML_C_WORDS = SegWork::C_WORDS;
-static_assert(ML_C_LATE < ML_C_WORDS && TS_C_WORDS <= ML_C_LATE, "the shared workspace's counter words");
-// txn word: state << 16 | cap << 8 | progress (waitdie.hip's)
-constexpr uint32_t MS_UND = 0, MS_OK = 1, MS_WAIT = 2, MS_ABORT = 3, MS_STATIC = 4, MS_NOCAP = 0xFFu;
-__host__ __device__ constexpr uint32_t ms_word(uint32_t state, uint32_t cap, uint32_t prog) {
-  return (state << 16) | (cap << 8) | prog;
-}
-__device__ inline uint32_t ms_state(uint32_t w) { return w >> 16; }
-__device__ inline uint32_t ms_cap(uint32_t w) { return (w >> 8) & 0xFFu; }
-__device__ inline uint32_t ms_prog(uint32_t w) { return w & 0xFFu; }
+static_assert(lv_word_free(TS_C_HEADS) && lv_word_free(TS_C_ROWS) && lv_word_free(ML_C_NC) &&
+                  lv_word_free(ML_C_NC + 1) && LV_C_RING == TS_C_RING && LV_C_WORDS <= ML_C_LATE &&
+                  ML_C_LATE < ML_C_WORDS,
+              "the shared workspace's counter words");
 // record word: position | type << 8 | kind << 10 | TS_I_HEAD | TS_I_LAST.
 // Epoch kinds: a static prewrite, a dynamic access.  Finish kinds are bits: a
 // version to install, a remaining prewrite, a buffered read.
@@ -113,122 +107,29 @@ __device__ inline uint32_t mi_kind(uint32_t info) { return (info >> 10) & 7u; }
 // flag byte of a dynamic access: abort / wait under the certain sets, under the possible sets
 constexpr uint32_t MF_CA = 1, MF_CW = 2, MF_PA = 4, MF_PW = 8;
 
-__device__ inline bool ml_state_ok(uint8_t rc) {
-  return rc == DCC_WD_RUN || rc == DCC_RC_RCOK || rc == DCC_RC_WAIT || rc == DCC_RC_ABORT || rc == DCC_WD_GONE;
-}
-
-// ---------------------------------------------------------------- check
-// The batch's and the state's validity before anything indexes with them and
-// before anything is written; the key bits that vary; the RUN txns (epoch,
-// `leave` null: the ring word round 1 reads) or, for a finish, the leavers
-// that were not GONE and the timestamp bits that vary.
-__global__ __launch_bounds__(TS_T) void k_ml_check(const uint32_t* __restrict__ off, uint64_t n,
-                                                   const uint64_t* __restrict__ keys, uint64_t nnz,
-                                                   const uint64_t* __restrict__ ts,
-                                                   const uint8_t* __restrict__ rc,
-                                                   const uint32_t* __restrict__ pos,
-                                                   const uint8_t* __restrict__ leave, uint32_t* __restrict__ cnt) {
-  __shared__ uint64_t s_a[TS_T / 64], s_b[TS_T / 64], s_e[TS_T / 64], s_f[TS_T / 64];
-  __shared__ uint32_t s_c[TS_T / 64], s_d[TS_T / 64];
-  uint32_t len = 0, err = 0, count = 0;
-  uint64_t kor = 0, knor = 0, tor = 0, tnor = 0;
-  const uint64_t tid = (uint64_t)blockIdx.x * TS_T + threadIdx.x, stride = (uint64_t)gridDim.x * TS_T;
-  for (uint64_t t = tid; t < n; t += stride) {
-    uint32_t l;
-    if (!check_span(off, t, n, nnz, err, len, l)) continue;
-    const uint8_t r = rc[t];
-    const uint32_t p = pos[t];
-    const uint64_t v = ts[t];
-    if (!ml_state_ok(r)) err |= ML_ERR_RC;
-    else if (r != DCC_WD_GONE && (p > l || (r == DCC_RC_RCOK && p != l) || (r == DCC_RC_WAIT && p >= l)))
-      err |= ML_ERR_POS;
-    if (r != DCC_WD_GONE && (v == 0 || v == ~0ull)) err |= TS_ERR_TS;
-    if (leave && leave[t] != 0 && r == DCC_RC_WAIT) err |= ML_ERR_LEAVE;
-    tor |= v;
-    tnor |= ~v;
-    count += leave ? (leave[t] != 0 && r != DCC_WD_GONE) : (r == DCC_WD_RUN);
+// live_txn.h's engine type
+struct MlLive {
+  static constexpr uint32_t T = TS_T;
+  static constexpr const char* name = "mvcc";
+  static constexpr bool TS_RANGE = true, WAIT_STAYS = true, ROW_BIT = false, ABORT_POS = true;
+  // dynamic from the pos of a RUN txn on; a prewrite: a WR below pos, or at
+  // the pos of a WAIT txn; the WR requests are the counted ones
+  __device__ static uint32_t record(uint8_t r, uint32_t p, uint32_t a, uint32_t ty, bool& dyn, bool& req) {
+    const bool wr = ty == DCC_WR;
+    uint32_t kind = MK_NONE;
+    if (r == DCC_WD_RUN && a >= p) kind = MK_DYN;
+    else if (r != DCC_WD_GONE && wr && (a < p || (r == DCC_RC_WAIT && a == p))) kind = MK_PRE;
+    dyn = kind == MK_DYN;
+    req = dyn && wr;
+    return (ty << 8) | (kind << 10);
   }
-  for (uint64_t x = tid; x < nnz; x += stride) check_key(keys[x], err, kor, knor);
-  kor = block_reduce<TS_T / 64, OrOp<uint64_t>>(kor, s_a);
-  knor = block_reduce<TS_T / 64, OrOp<uint64_t>>(knor, s_b);
-  tor = block_reduce<TS_T / 64, OrOp<uint64_t>>(tor, s_e);
-  tnor = block_reduce<TS_T / 64, OrOp<uint64_t>>(tnor, s_f);
-  len = block_reduce<TS_T / 64, MaxOp<uint32_t>>(len, s_c);
-  err = block_reduce<TS_T / 64, OrOp<uint32_t>>(err, s_d);
-  if (threadIdx.x == 0) {
-    if (kor) atomicOr((unsigned long long*)&cnt[SEG_C_KOR], (unsigned long long)kor);
-    if (knor) atomicOr((unsigned long long*)&cnt[SEG_C_KNOR], (unsigned long long)knor);
-    if (leave && tor) atomicOr((unsigned long long*)&cnt[ML_C_TOR], (unsigned long long)tor);
-    if (leave && tnor) atomicOr((unsigned long long*)&cnt[ML_C_TNOR], (unsigned long long)tnor);
-    if (len) atomicMax(&cnt[SEG_C_MAXLEN], len);
-    if (err) atomicOr(&cnt[SEG_C_ERR], err);
+  // a possible abort or wait stops; a certain abort aborts, a certain wait
+  // without a possible abort waits
+  static constexpr uint32_t STOP = MF_PA | MF_PW, CERTAIN = MF_CA | MF_CW;
+  __device__ static uint32_t verdict(uint32_t f) {
+    return (f & MF_CA) ? LS_ABORT : ((f & MF_CW) && !(f & MF_PA) ? LS_WAIT : LS_UND);
   }
-  block_add<TS_T / 64>(count, leave ? &cnt[ML_C_LEFT] : &cnt[TS_C_RING + 1]);
-}
-
-struct MlArgs {
-  uint64_t n, m;
-  const uint32_t* off;
-  const uint64_t* keys;
-  const uint8_t* at;
-  const uint64_t* ts;
-  uint8_t* rc;       // the state, updated in place behind the decisions
-  uint32_t* pos;
-  uint32_t lp;       // log2 lanes per txn
-  uint4* arec;       // [m] {txn, record word, ts lo, ts hi} of every access
-  uint32_t* stp;     // [n] txn words
-  uint8_t* flg;      // [m] MF_* of every dynamic access, batch order
-  uint32_t* cnt;
 };
-
-// P lanes per txn (nowait_lanes.h).  Epoch: the sort key (packed row, dynamic)
-// and the record of every access; a RUN txn undecided at progress pos; the WR
-// requests and the RUN txns without one counted.
-__global__ __launch_bounds__(TS_T) void k_ml_prep(MlArgs A, KeyPack kp, uint64_t* __restrict__ ak,
-                                                  uint32_t* __restrict__ av) {
-  const Seg g = seg_of(A.lp);
-  const uint32_t gpb = TS_T >> A.lp;
-  uint32_t ro = 0, nwr = 0;
-  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
-    const uint64_t t = g0 + g.gl;
-    const bool tv = t < A.n;
-    uint32_t o0 = 0, len = 0, p = 0;
-    uint8_t r = DCC_WD_GONE;
-    uint64_t tsv = 0;
-    if (tv) {
-      o0 = A.off[t];
-      len = A.off[t + 1] - o0;
-      tsv = A.ts[t];
-      r = A.rc[t];
-      p = A.pos[t];
-    }
-    const bool v = tv && g.a < len, run = r == DCC_WD_RUN;
-    const uint64_t x = (uint64_t)o0 + g.a;
-    bool wreq = false;
-    if (v) {
-      const uint32_t ty = A.at[x] & 3u;
-      const bool wr = ty == DCC_WR;
-      uint32_t kind = MK_NONE;
-      if (run && g.a >= p) kind = MK_DYN;
-      else if (r != DCC_WD_GONE && wr && (g.a < p || (r == DCC_RC_WAIT && g.a == p))) kind = MK_PRE;
-      wreq = kind == MK_DYN && wr;
-      ak[x] = (keypack_apply(kp, A.keys[x]) << 1) | (kind == MK_DYN ? 1ull : 0ull);
-      av[x] = (uint32_t)x;
-      A.arec[x] = make_uint4((uint32_t)t, g.a | (ty << 8) | (kind << 10), (uint32_t)tsv, (uint32_t)(tsv >> 32));
-    }
-    const uint64_t wb = ballot64(wreq) & g.mask;
-    if (tv && g.a == 0) {
-      A.stp[t] = run ? ms_word(MS_UND, MS_NOCAP, p) : ms_word(MS_STATIC, 0, 0);
-      if (run) {
-        ro += wb ? 0u : 1u;
-        nwr += (uint32_t)__popcll(wb);
-      }
-    }
-  }
-  block_add<TS_T / 64>(ro, &A.cnt[TS_C_RO]);
-  __syncthreads();  // block_add's LDS words are read before the next call writes them
-  block_add<TS_T / 64>(nwr, &A.cnt[TS_C_NWR]);
-}
 
 // The sorted records: sk / sv are the sorted keys (the packed row above
 // `shift` bits) and access indices; the rows counted.
@@ -280,10 +181,10 @@ struct MlScan {
 template <bool FINAL>
 __device__ inline Tq ml_elem(uint32_t info, uint32_t st, uint64_t ts, uint32_t slot, const RowSlot* tab) {
   const uint32_t q = info & 0xFFu, ty = mi_type(info), kind = mi_kind(info);
-  const uint32_t state = ms_state(st), p = ms_prog(st), cap = ms_cap(st);
-  const bool dyn = kind == MK_DYN, nx = ty != DCC_XP, wr = ty == DCC_WR, und = state == MS_UND;
-  const bool cex = dyn && nx && (state == MS_OK || q < p);
-  const bool cpr = kind == MK_PRE || (dyn && wr && (state == MS_OK || q < p || (state == MS_WAIT && q == p)));
+  const uint32_t state = ls_state(st), p = ls_prog(st), cap = ls_cap(st);
+  const bool dyn = kind == MK_DYN, nx = ty != DCC_XP, wr = ty == DCC_WR, und = state == LS_UND;
+  const bool cex = dyn && nx && (state == LS_OK || q < p);
+  const bool cpr = kind == MK_PRE || (dyn && wr && (state == LS_OK || q < p || (state == LS_WAIT && q == p)));
   const bool pex = cex || (dyn && und && nx && q < cap);
   const bool ppr = cpr || (dyn && und && wr && q <= cap);
   Tq e;
@@ -324,7 +225,7 @@ __global__ __launch_bounds__(TS_T) void k_ml_scan(MlScan A) {
   for (uint32_t k = 0; k < TS_ITEMS; k++) {
     const bool v = base + k < A.m;
     info[k] = v ? A.s_info[base + k] : 0u;  // past the end: an identity element
-    st[k] = v ? A.stp[A.s_txn[base + k]] : ms_word(MS_STATIC, 0, 0);
+    st[k] = v ? A.stp[A.s_txn[base + k]] : ls_word(LS_STATIC, 0, 0);
     ts[k] = v ? A.s_ts[base + k] : 0;
   }
   Tq mine = TqOp::identity();
@@ -339,7 +240,7 @@ __global__ __launch_bounds__(TS_T) void k_ml_scan(MlScan A) {
   if (!APPLY) {
     bool und = false;
 #pragma unroll
-    for (uint32_t k = 0; k < TS_ITEMS; k++) und |= ms_state(st[k]) == MS_UND;
+    for (uint32_t k = 0; k < TS_ITEMS; k++) und |= ls_state(st[k]) == LS_UND;
     const bool any = !FINAL && __syncthreads_or(und);
     if (threadIdx.x == 0) {
       A.agg[blockIdx.x] = total;
@@ -359,11 +260,11 @@ __global__ __launch_bounds__(TS_T) void k_ml_scan(MlScan A) {
     const Tq b = (info[k] & TS_I_HEAD) ? e[k] : run;
     const uint64_t t = ts[k];
     if (!FINAL) {
-      if (v && dyn && ms_state(st[k]) == MS_UND && q >= ms_prog(st[k])) {
+      if (v && dyn && ls_state(st[k]) == LS_UND && q >= ls_prog(st[k])) {
         A.flg[A.sv[base + k]] = (uint8_t)((wr && t < b.de ? MF_CA : 0u) | (nx && b.dw > ~t ? MF_CW : 0u) |
                                           (wr && t < b.pe ? MF_PA : 0u) | (nx && b.pw > ~t ? MF_PW : 0u));
       }
-    } else if (v && dyn && nx && A.vts && (ms_state(st[k]) == MS_OK || q < ms_prog(st[k]))) {
+    } else if (v && dyn && nx && A.vts && (ls_state(st[k]) == LS_OK || q < ls_prog(st[k]))) {
       const uint32_t x = A.sv[base + k];
       uint64_t ver = b.dw;  // the row's latest version
       if (t < ver) {
@@ -383,88 +284,13 @@ __global__ __launch_bounds__(TS_T) void k_ml_scan(MlScan A) {
   if (FINAL) block_add<TS_T / 64>(late, &A.cnt[ML_C_LATE]);
 }
 
-// One round of decisions.  P lanes per txn, one access per lane: the first
-// access at or past the progress with a possible stop is where the txn aborts,
-// waits or stays undecided.  Counts the txns it leaves undecided.
-__global__ __launch_bounds__(TS_T) void k_ml_advance(MlArgs A, const uint32_t* __restrict__ left,
-                                                     uint32_t* left_out) {
-  if (*left == 0) return;
-  const Seg g = seg_of(A.lp);
-  const uint32_t gpb = TS_T >> A.lp;
-  uint32_t und_left = 0;
-  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
-    const uint64_t t = g0 + g.gl;
-    const bool tv = t < A.n;
-    const uint32_t st = tv ? A.stp[t] : ms_word(MS_STATIC, 0, 0);
-    const bool und = tv && ms_state(st) == MS_UND;
-    if (!ballot64(und)) continue;  // the wave's txns are decided
-    uint32_t o0 = 0, len = 0;
-    if (und) {
-      o0 = A.off[t];
-      len = A.off[t + 1] - o0;
-    }
-    const bool v = und && g.a < len && g.a >= ms_prog(st);
-    const uint32_t f = v ? A.flg[(uint64_t)o0 + g.a] : 0u;
-    const uint64_t sb = ballot64((f & (MF_PA | MF_PW)) != 0) & g.mask;
-    const uint64_t cab = ballot64((f & MF_CA) != 0), cwb = ballot64((f & MF_CW) != 0),
-                   pab = ballot64((f & MF_PA) != 0);
-    if (und && g.a == 0) {
-      uint32_t w;
-      if (!sb) {
-        w = ms_word(MS_OK, 0, len);
-      } else {
-        const uint32_t l = (uint32_t)__builtin_ctzll(sb);
-        const bool ca = (cab >> l) & 1ull, cw = (cwb >> l) & 1ull, pa = (pab >> l) & 1ull;
-        const uint32_t s = ca ? MS_ABORT : (cw && !pa ? MS_WAIT : MS_UND);
-        const uint64_t cf = (cab | cwb) & g.mask;  // certain stops at or past the progress: they stay certain
-        w = ms_word(s, cf ? (uint32_t)__builtin_ctzll(cf) - g.seg0 : MS_NOCAP, l - g.seg0);
-        und_left += s == MS_UND ? 1u : 0u;
-      }
-      A.stp[t] = w;
-    }
-  }
-  block_add<TS_T / 64>(und_left, left_out);
-}
-
-// The new state of the RUN txns: (RCOK, len), (WAIT, stop) or (ABORT, stop);
-// the conflict ordinals; the counts.
-__global__ __launch_bounds__(TS_T) void k_ml_final(uint64_t n, const uint32_t* __restrict__ stp,
-                                                   uint8_t* __restrict__ rc, uint32_t* __restrict__ pos,
-                                                   uint32_t* __restrict__ conflict, uint32_t* __restrict__ cnt) {
-  uint32_t ok = 0, ab = 0, wait = 0, bad = 0;
-  for (uint64_t t = (uint64_t)blockIdx.x * TS_T + threadIdx.x; t < n; t += (uint64_t)gridDim.x * TS_T) {
-    const uint32_t st = stp[t], s = ms_state(st), p = ms_prog(st);
-    uint32_t c = DCC_ACCESS_NONE;
-    if (s == MS_OK) {
-      rc[t] = DCC_RC_RCOK;
-      pos[t] = p;
-      ok++;
-    } else if (s == MS_WAIT || s == MS_ABORT) {
-      rc[t] = s == MS_WAIT ? DCC_RC_WAIT : DCC_RC_ABORT;
-      pos[t] = p;
-      c = p;
-      wait += s == MS_WAIT;
-      ab += s == MS_ABORT;
-    } else if (s == MS_UND) {
-      bad = 1;
-    }
-    if (conflict) conflict[t] = c;
-  }
-  if (bad) atomicOr(&cnt[SEG_C_ERR], TS_ERR_STATE);
-  block_add<TS_T / 64>(ok, &cnt[TS_C_COMMIT]);
-  __syncthreads();
-  block_add<TS_T / 64>(ab, &cnt[ML_C_ABORT]);
-  __syncthreads();
-  block_add<TS_T / 64>(wait, &cnt[ML_C_WAIT]);
-}
-
 // --------------------------------------------------------------- finish
 // P lanes per txn: the first sort's key of every access, its txn's packed ts
 // (ascending; input order is txn index order, which the stable sorts keep),
 // and its record: the WR accesses of a committing leaver install a version;
 // a staying txn's prewrites remain, and so does its buffered read.  The
 // versions to install counted.
-__global__ __launch_bounds__(TS_T) void k_ml_fprep(MlArgs A, const uint8_t* __restrict__ leave, KeyPack tp,
+__global__ __launch_bounds__(TS_T) void k_ml_fprep(LiveArgs A, const uint8_t* __restrict__ leave, KeyPack tp,
                                                    uint64_t* __restrict__ ak, uint32_t* __restrict__ av) {
   const Seg g = seg_of(A.lp);
   const uint32_t gpb = TS_T >> A.lp;
@@ -620,96 +446,31 @@ __global__ __launch_bounds__(TS_T) void k_ml_fscan(MlFin A) {
       r->*WTS = max(r->*WTS, run.pw);
     }
   }
-  block_add<TS_T / 64>(prom, &A.cnt[ML_C_PROM]);
+  block_add<TS_T / 64>(prom, &A.cnt[LV_C_PROM]);
 }
 
-__global__ __launch_bounds__(TS_T) void k_ml_gone(uint64_t n, const uint8_t* __restrict__ leave,
-                                                  uint8_t* __restrict__ rc, const uint32_t* __restrict__ err) {
-  if (*err) return;
-  for (uint64_t t = (uint64_t)blockIdx.x * TS_T + threadIdx.x; t < n; t += (uint64_t)gridDim.x * TS_T)
-    if (leave[t]) rc[t] = DCC_WD_GONE;
-}
-
-// What an epoch and a finish share up to ev0: the call's arguments checked,
-// the batch and the state arrays on the device, the check, the key pack and
-// the lanes' geometry.  A.n == 0 behind a DCC_OK: the empty batch.
-struct MlOpen {
-  uint64_t per_block = 0, tiles = 0, tvar = 0;
-  uint32_t count = 0;  // the RUN txns, or the leavers that were not GONE
-  bool dev = false;
-  const uint8_t* leave_dev = nullptr;
-  uint64_t* vts_dev = nullptr;
-  unsigned max_grid = 1;
-  BatchShape c;
-  KeyPack kp{};
-  DevBatch d;
-  MlArgs A{};
-};
+// live_txn.h's open, and behind it what MVCC adds: its own workspaces and the
+// versions of a host call on the device (a call writes some entries and leaves
+// the others alone).
 int ml_open(dcc_ctx* ctx, const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_io, uint32_t* pos_io, bool finish,
-            const uint8_t* leave_in, uint64_t* vts_io, uint64_t* out_left, uint64_t* out_promoted, MlOpen& O) {
-  hipStream_t stream = ctx->stream;
-  if (!ts_in || !rc_io || !pos_io) return ctx->fail(DCC_EINVAL, "mvcc: null ts / rc / pos");
-  if (finish && !leave_in) return ctx->fail(DCC_EINVAL, "mvcc: null leave");
-  CR(ctx->check_batch(b, false));  // the offsets are checked on the device (k_ml_check)
-  if (ctx->comm_ranks() > 1) return ctx->fail(DCC_ENOTSUP, "mvcc: single-GPU engine");
-  O.dev = (b->flags & DCC_DEVICE_PTRS) != 0;
-  if (out_left) *out_left = 0;
-  if (out_promoted) *out_promoted = 0;
-  if (b->n_txn == 0) return DCC_OK;
-  CR(ctx->stage_batch(b, O.d));
-  const DevBatch& d = O.d;
-  const uint64_t n = d.n, m = d.nnz;
-  CR(ctx->mvcc_live_reserve(n, m, !O.dev));
-  const uint64_t* ts_dev;
-  uint8_t* rc_dev;
-  uint32_t* pos_dev;
-  CR(ctx->waitdie_stage(n, O.dev, ts_in, rc_io, pos_io, leave_in, ts_dev, rc_dev, pos_dev, O.leave_dev));
-  O.vts_dev = vts_io;
-  if (vts_io && !O.dev) {  // a call writes some entries and leaves the others alone
-    O.vts_dev = (uint64_t*)ctx->mv_vts.p;
-    if (m) CK(hipMemcpyAsync(O.vts_dev, vts_io, m * 8, hipMemcpyHostToDevice, stream));
+            const uint8_t* leave_in, uint64_t* vts_io, uint64_t* out_left, uint64_t* out_promoted, LiveOpen& O,
+            uint64_t*& vts_dev) {
+  CR(live_open<MlLive>(ctx, b, ts_in, rc_io, pos_io, finish, leave_in, out_left, out_promoted, O));
+  vts_dev = vts_io;
+  if (O.A.n == 0) return DCC_OK;
+  // live_open has made live_reserve's part with the same sizes, so that part
+  // allocates nothing here and the pointers in O.A stay valid
+  CR(ctx->mvcc_live_reserve(O.A.n, O.A.m, !O.dev));
+  if (vts_io && !O.dev) {
+    vts_dev = (uint64_t*)ctx->mv_vts.p;
+    if (O.A.m) CK(hipMemcpyAsync(vts_dev, vts_io, O.A.m * 8, hipMemcpyHostToDevice, ctx->stream));
   }
-  SegWork& W = ctx->seg;
-  uint32_t* cnt = (uint32_t*)W.misc.p;
-  O.max_grid = (unsigned)ctx->n_cu * 16;
-
-  // reject a malformed batch or state before anything indexes with it: rc,
-  // pos, the outputs, the rows and the store are untouched by a rejected call
-  CK(hipMemsetAsync(cnt, 0, ML_C_WORDS * 4, stream));
-  k_ml_check<<<launch_grid(std::max(n, m), TS_T * 4, O.max_grid), TS_T, 0, stream>>>(
-      d.off, n, d.keys, m, ts_dev, rc_dev, pos_dev, O.leave_dev, cnt);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(ctx->hmisc, cnt, ML_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  const uint32_t* hc = (const uint32_t*)ctx->hmisc;
-  const uint32_t err = hc[SEG_C_ERR];
-  CR(batch_checked(ctx, hc, m, true, O.c));
-  if (err & ML_ERR_RC) return ctx->fail(DCC_EINVAL, "mvcc: an rc byte is none of the five states");
-  if (err & ML_ERR_POS)
-    return ctx->fail(DCC_EINVAL, "mvcc: a pos does not fit its state (pos > len, RCOK below len, WAIT at len)");
-  if (err & TS_ERR_TS) return ctx->fail(DCC_EINVAL, "mvcc: a timestamp is 0 or UINT64_MAX");
-  if (err & ML_ERR_LEAVE) return ctx->fail(DCC_EINVAL, "mvcc: a WAIT txn cannot leave");
-  if (finish) {
-    uint64_t a, o;
-    memcpy(&a, hc + ML_C_TOR, 8);
-    memcpy(&o, hc + ML_C_TNOR, 8);
-    O.tvar = a & o;
-    O.count = hc[ML_C_LEFT];
-  } else {
-    O.count = hc[TS_C_RING + 1];
-  }
-  O.kp = make_keypack(O.c.varying);
-  if (!finish && O.kp.bits > 63) return ctx->fail(DCC_ENOTSUP, "mvcc: the keys vary in all 64 bits");
-  O.per_block = TS_T >> O.c.lp;
-  O.tiles = (m + TS_TILE - 1) / TS_TILE;
-  O.A = MlArgs{n,      m,  d.off, d.keys, d.acctype, ts_dev, rc_dev, pos_dev,
-               O.c.lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p, (uint8_t*)ctx->wd_flg.p, cnt};
   return DCC_OK;
 }
 
 // The rows of the sorted records entered into the table, which gets room for
 // every one of them first (`heads`, read back by the caller).
-int ml_seed(dcc_ctx* ctx, const MlOpen& O, uint32_t heads, const uint32_t* sv) {
+int ml_seed(dcc_ctx* ctx, const LiveOpen& O, uint32_t heads, const uint32_t* sv) {
   hipStream_t stream = ctx->stream;
   RowTab& rows = ctx->mv_rows;
   CR(rows.reserve<TsProbe>(ctx, rows.rows + heads));
@@ -725,7 +486,7 @@ int ml_seed(dcc_ctx* ctx, const MlOpen& O, uint32_t heads, const uint32_t* sv) {
 int dcc_ctx::mvcc_live_reserve(uint64_t n, uint64_t nnz, bool host_arrays) {
   const uint64_t mm = std::max<uint64_t>(nnz, 1);
   const uint64_t mt = (mm + TS_TILE - 1) / TS_TILE * TS_TILE;
-  CR(waitdie_reserve(n, nnz, host_arrays));  // `seg`, the flag bytes, the state arrays of a host call
+  CR(live_reserve(n, nnz, host_arrays));  // `seg`, the flag bytes, the state arrays of a host call
   CR(ts_hslot.ensure(this, mt * 4, "mvcc head slots"));
   CR(mv_ek.ensure(this, mt * 8, "mvcc epoch version keys"));
   CR(mv_et.ensure(this, mt * 8, "mvcc epoch version timestamps"));
@@ -737,10 +498,10 @@ int dcc_ctx::mvcc_live_reserve(uint64_t n, uint64_t nnz, bool host_arrays) {
 int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_io, uint32_t* pos_io,
                                uint64_t* vts_io, uint32_t* out_conflict, dcc_stats* st) {
   dcc_ctx* ctx = this;
-  EpochStats es;
-  dcc_stats& S = es.S;
-  MlOpen O;
-  CR(ml_open(this, b, ts_in, rc_io, pos_io, false, nullptr, vts_io, nullptr, nullptr, O));
+  LiveOpen O;
+  dcc_stats& S = O.es.S;
+  uint64_t* vts_dev;
+  CR(ml_open(this, b, ts_in, rc_io, pos_io, false, nullptr, vts_io, nullptr, nullptr, O, vts_dev));
   if (O.A.n == 0) {
     if (st) *st = S;
     return DCC_OK;
@@ -749,8 +510,8 @@ int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_
   const bool dev = O.dev, prof = profiling;
   const unsigned max_grid = O.max_grid;
   const KeyPack kp = O.kp;
-  const MlArgs& A = O.A;
-  uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)wd_conf.p) : nullptr;
+  const LiveArgs& A = O.A;
+  uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)lv_conf.p) : nullptr;
   SegWork& W = seg;
   uint32_t* cnt = A.cnt;
 
@@ -759,7 +520,7 @@ int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_
   uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
   uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
   const unsigned agrid = launch_grid(n, O.per_block, max_grid);
-  k_ml_prep<<<agrid, TS_T, 0, stream>>>(A, kp, kb[0], vb[0]);
+  k_live_prep<MlLive><<<agrid, TS_T, 0, stream>>>(A, kp, kb[0], vb[0]);
   CK(hipGetLastError());
   MlScan SA{};
   if (m) {
@@ -768,7 +529,7 @@ int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_
                                                                   (uint32_t*)W.sinfo.p, (uint64_t*)W.sts.p, cnt);
     CK(hipGetLastError());
     // the table gets room for every row of the epoch before any is entered
-    CK(hipMemcpyAsync(hmisc, cnt, TS_C_RING * 4, hipMemcpyDeviceToHost, stream));
+    CK(hipMemcpyAsync(hmisc, cnt, LV_C_RING * 4, hipMemcpyDeviceToHost, stream));
     CK(hipStreamSynchronize(stream));
     CR(ml_seed(this, O, ((const uint32_t*)hmisc)[TS_C_HEADS], vb[cur]));
     CK(hipMemsetAsync(W.tdone.p, 0, tiles, stream));
@@ -788,7 +549,7 @@ int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_
                 cnt,
                 A.keys,
                 MvStore{(const uint64_t*)mv_sk[mv_cur].p, (const uint64_t*)mv_st[mv_cur].p, mv_n},
-                O.vts_dev};
+                vts_dev};
   }
   if (prof) CK(hipEventRecord(pev[1], stream));
 
@@ -796,7 +557,7 @@ int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_
   // which clears the ring word the round counts into / apply / advance.  The
   // lowest undecided txn is decided in every round.
   uint32_t rounds = 0;
-  CR(rounds_loop(this, cnt + TS_C_RING, n, n + m + 2, "mvcc", rounds,
+  CR(rounds_loop(this, cnt + LV_C_RING, n, n + m + 2, MlLive::name, rounds,
                  [&](uint32_t, const uint32_t* left, uint32_t* left_out, uint64_t) {
                    if (m) {
                      SA.left = left;
@@ -806,13 +567,13 @@ int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_
                    } else {
                      k_tile_aggscan<TqOp><<<1, SEG_AGG_T, 0, stream>>>(nullptr, nullptr, 0, left, left_out);
                    }
-                   k_ml_advance<<<agrid, TS_T, 0, stream>>>(A, left, left_out);
+                   k_live_advance<MlLive><<<agrid, TS_T, 0, stream>>>(A, left, left_out);
                  }));
 
   // rc / pos of a host call stay as they were unless the decisions are sound:
   // the final pass writes the staged copies.  Versions and the rows' rts come
   // behind it and its error word.
-  k_ml_final<<<launch_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, A.stp, A.rc, A.pos, conf_dev, cnt);
+  k_live_final<MlLive><<<launch_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, A.stp, A.rc, A.pos, conf_dev, cnt);
   if (m) {
     k_ml_scan<false, true><<<(unsigned)tiles, TS_T, 0, stream>>>(SA);
     k_tile_aggscan<TqOp><<<1, SEG_AGG_T, 0, stream>>>(SA.agg, SA.pre, tiles, nullptr, nullptr);
@@ -828,20 +589,18 @@ int dcc_ctx::mvcc_access_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_
   if (hc[SEG_C_ERR] & TS_ERR_FULL) return fail(DCC_EIO, "mvcc: row table full");
   if (hc[SEG_C_ERR] & TS_ERR_STATE) return fail(DCC_EIO, "mvcc: inconsistent decisions");
   S.rounds = rounds;
-  S.n_commit = hc[TS_C_COMMIT];
-  S.n_abort = hc[ML_C_ABORT];
-  S.n_survivors = hc[ML_C_WAIT];
-  S.nnz_w = hc[TS_C_NWR];
-  S.n_readonly = hc[TS_C_RO];
+  S.n_commit = hc[LV_C_OK];
+  S.n_abort = hc[LV_C_ABORT];
+  S.n_survivors = hc[LV_C_WAIT];
+  S.nnz_w = hc[LV_C_NREQ];
+  S.n_readonly = hc[LV_C_RO];
   if (!dev) {
-    CK(hipMemcpyAsync(rc_io, A.rc, n, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(pos_io, A.pos, n * 4, hipMemcpyDeviceToHost, stream));
-    if (out_conflict) CK(hipMemcpyAsync(out_conflict, conf_dev, n * 4, hipMemcpyDeviceToHost, stream));
-    if (vts_io && m) CK(hipMemcpyAsync(vts_io, O.vts_dev, m * 8, hipMemcpyDeviceToHost, stream));
+    CR(live_copy_back(this, O, rc_io, pos_io, out_conflict));
+    if (vts_io && m) CK(hipMemcpyAsync(vts_io, vts_dev, m * 8, hipMemcpyDeviceToHost, stream));
     CK(hipStreamSynchronize(stream));
   }
   S.alg_bytes = dcc_mvcc_access_alg_bytes(n, m, out_conflict != nullptr, vts_io != nullptr);
-  CR(es.finish(this, 4));
+  CR(O.es.finish(this, 4));
   if (st) *st = S;
   return DCC_OK;
 }
@@ -850,10 +609,10 @@ int dcc_ctx::mvcc_finish(const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_
                          const uint8_t* leave_in, uint64_t* vts_io, uint64_t* out_left, uint64_t* out_promoted,
                          dcc_stats* st) {
   dcc_ctx* ctx = this;
-  EpochStats es;
-  dcc_stats& S = es.S;
-  MlOpen O;
-  CR(ml_open(this, b, ts_in, rc_io, pos_io, true, leave_in, vts_io, out_left, out_promoted, O));
+  LiveOpen O;
+  dcc_stats& S = O.es.S;
+  uint64_t* vts_dev;
+  CR(ml_open(this, b, ts_in, rc_io, pos_io, true, leave_in, vts_io, out_left, out_promoted, O, vts_dev));
   if (O.A.n == 0) {
     if (st) *st = S;
     return DCC_OK;
@@ -861,29 +620,26 @@ int dcc_ctx::mvcc_finish(const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_
   const uint64_t n = O.A.n, m = O.A.m, tiles = O.tiles;
   const unsigned max_grid = O.max_grid;
   const KeyPack kp = O.kp, tp = make_keypack(O.tvar);
-  const MlArgs& A = O.A;
+  const LiveArgs& A = O.A;
   SegWork& W = seg;
   uint32_t* cnt = A.cnt;
   uint64_t ninst = 0;
 
   CK(hipEventRecord(ev0, stream));
   if (m) {
-    uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
-    uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
     const unsigned mgrid = launch_grid(m, TS_T, max_grid);
+    const uint64_t* sk;
+    const uint32_t* sv;
     // the records hold what the passes below need of rc / pos / leave: the
     // state is only written behind them (the checked offsets cover every
     // access, so k_ml_fprep writes every key and record)
-    k_ml_fprep<<<launch_grid(n, O.per_block, max_grid), TS_T, 0, stream>>>(A, O.leave_dev, tp, kb[0], vb[0]);
-    CK(hipGetLastError());
-    const int c1 = radix_sort_u64(kb, vb, m, tp.bits, (uint32_t*)cv_scratch.p, stream);
-    uint64_t* kb2[2] = {kb[c1], kb[c1 ^ 1]};
-    uint32_t* vb2[2] = {vb[c1], vb[c1 ^ 1]};
-    k_ml_fkey<<<mgrid, TS_T, 0, stream>>>(m, A.keys, kp, vb2[0], kb2[0]);
-    CK(hipGetLastError());
-    const int c2 = radix_sort_u64(kb2, vb2, m, kp.bits, (uint32_t*)cv_scratch.p, stream);
-    const uint32_t* sv = vb2[c2];
-    k_ml_seg<<<mgrid, TS_T, 0, stream>>>(m, 0, A.arec, kb2[c2], sv, (uint32_t*)W.stxn.p, (uint32_t*)W.sinfo.p,
+    CR(live_sort_ts_row(
+        this, m, tp.bits, kp.bits,
+        [&](uint64_t* ak, uint32_t* av) {
+          k_ml_fprep<<<launch_grid(n, O.per_block, max_grid), TS_T, 0, stream>>>(A, O.leave_dev, tp, ak, av);
+        },
+        [&](const uint32_t* v, uint64_t* k) { k_ml_fkey<<<mgrid, TS_T, 0, stream>>>(m, A.keys, kp, v, k); }, sk, sv));
+    k_ml_seg<<<mgrid, TS_T, 0, stream>>>(m, 0, A.arec, sk, sv, (uint32_t*)W.stxn.p, (uint32_t*)W.sinfo.p,
                                          (uint64_t*)W.sts.p, cnt);
     CK(hipGetLastError());
     // room in the row table for every row and in the store's other buffer for
@@ -912,14 +668,14 @@ int dcc_ctx::mvcc_finish(const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_
       store = MvStore{dk, dt, mv_n + ninst};
     }
     const MlFin F{m,     (const uint32_t*)W.stxn.p, s_info,  s_ts, sv,    (const uint32_t*)ts_hslot.p,
-                  (RowSlot*)mv_rows.buf.p, (Tq*)W.agg.p, (Tq*)W.agg.p + tiles, A.keys, store, O.vts_dev,
+                  (RowSlot*)mv_rows.buf.p, (Tq*)W.agg.p, (Tq*)W.agg.p + tiles, A.keys, store, vts_dev,
                   A.rc,  A.pos, cnt};
     k_ml_fscan<false><<<(unsigned)tiles, TS_T, 0, stream>>>(F);
     k_tile_aggscan<TqOp><<<1, SEG_AGG_T, 0, stream>>>(F.agg, F.pre, tiles, nullptr, nullptr);
     k_ml_fscan<true><<<(unsigned)tiles, TS_T, 0, stream>>>(F);
     CK(hipGetLastError());
   }
-  k_ml_gone<<<launch_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, O.leave_dev, A.rc, &cnt[SEG_C_ERR]);
+  k_live_gone<MlLive><<<launch_grid(n, TS_T, max_grid), TS_T, 0, stream>>>(n, O.leave_dev, A.rc, &cnt[SEG_C_ERR]);
   CK(hipGetLastError());
   CK(hipEventRecord(ev1, stream));
   CK(hipMemcpyAsync(hmisc, cnt, ML_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
@@ -936,17 +692,16 @@ int dcc_ctx::mvcc_finish(const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_
     mv_n += nc;
   }
   if (!O.dev) {
-    CK(hipMemcpyAsync(rc_io, A.rc, n, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(pos_io, A.pos, n * 4, hipMemcpyDeviceToHost, stream));
-    if (vts_io && m) CK(hipMemcpyAsync(vts_io, O.vts_dev, m * 8, hipMemcpyDeviceToHost, stream));
+    CR(live_copy_back(this, O, rc_io, pos_io));
+    if (vts_io && m) CK(hipMemcpyAsync(vts_io, vts_dev, m * 8, hipMemcpyDeviceToHost, stream));
     CK(hipStreamSynchronize(stream));
   }
   S.n_commit = O.count;
-  S.n_survivors = hc[ML_C_PROM];
+  S.n_survivors = hc[LV_C_PROM];
   S.nnz_w = nc;
   if (out_left) *out_left = S.n_commit;
   if (out_promoted) *out_promoted = S.n_survivors;
-  CR(es.finish(this, 0));
+  CR(O.es.finish(this, 0));
   if (st) *st = S;
   return DCC_OK;
 }

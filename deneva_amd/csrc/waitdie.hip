@@ -51,15 +51,14 @@
 // iff no EX owner remains and it is the head of a row without owners or every
 // waiter up to it, itself included, is SH (row_lock.cpp:317-357).
 //
-// Kernels:  k_wd_check    offsets / keys / longest txn / the (rc, pos) state /
-//                         varying bits of the keys and the timestamps
-//           k_wd_prep     sort keys, access records, txn words, request counts
+// Kernels:  k_live_check / k_live_prep / k_live_advance / k_live_final /
+//           k_live_gone   live_txn.h's, with WdLive below: the
+//                         check, sort keys / records / txn words, one round of
+//                         decisions, rc / pos / conflict ordinals, the leavers
 //           k_wd_seg      sorted records, row heads, own-run heads
 //           k_wd_scan     per 1,024-access tile: its aggregate, or behind the
 //                         scanned aggregates four bits per dynamic access
-//           k_wd_advance  one round of decisions
-//           k_wd_final    rc, pos, conflict ordinals, counts
-//           k_wd_rprep / k_wd_rkey / k_wd_rseg / k_wd_rscan / k_wd_rgone: the release
+//           k_wd_rprep / k_wd_rkey / k_wd_rseg / k_wd_rscan: the release
 // No workgroup waits on another.  The offsets' and keys' rules of the check,
 // k_tile_aggscan, the rounds loop and the workspaces are seg_rounds.h's
 // (DESIGN.md §8n).
@@ -72,6 +71,7 @@
 #include "dcc_ctx.h"
 #include "dcc_device.h"
 #include "dcc_scan.h"
+#include "live_txn.h"
 #include "nowait_lanes.h"
 #include "occ_kernels.h"
 #include "radix_sort.h"
@@ -88,23 +88,7 @@ constexpr uint32_t WD_TILE = WD_T * WD_ITEMS;  // accesses per scan tile
 // where the tests that size their chains past it read the geometry
 constexpr uint32_t WD_RING = 64;
 static_assert(WD_RING == SEG_RING, "the ring is seg_rounds.h's");
-// error bits next to CHK_ERR_*
-constexpr uint32_t WD_ERR_RC = 4, WD_ERR_POS = 8, WD_ERR_STATE = 16;
-// counter words next to SEG_C_*; TOR / TNOR are u64 at words 12, 14
-constexpr uint32_t WD_C_NEX = 2, WD_C_RO = 3, WD_C_OK = 4, WD_C_DIE = 5, WD_C_WAIT = 6, WD_C_LEFT = 7,
-                   WD_C_TOR = 12, WD_C_TNOR = 14, WD_C_PROM = 16, WD_C_RING = 20,
-                   WD_C_WORDS = WD_C_RING + SEG_RING;
-static_assert(WD_TILE == SegWork::TILE && WD_C_WORDS <= SegWork::C_WORDS, "the shared workspace's sizes");
-// txn word: state << 16 | cap << 8 | progress.  cap: the first access at or
-// past the progress of an undecided txn with a certain conflict (WS_NOCAP: none
-// known): it owns nothing from there on and waits there at the latest
-constexpr uint32_t WS_UND = 0, WS_OK = 1, WS_WAIT = 2, WS_DIE = 3, WS_STATIC = 4, WS_NOCAP = 0xFFu;
-__host__ __device__ constexpr uint32_t ws_word(uint32_t state, uint32_t cap, uint32_t prog) {
-  return (state << 16) | (cap << 8) | prog;
-}
-__device__ inline uint32_t ws_state(uint32_t w) { return w >> 16; }
-__device__ inline uint32_t ws_cap(uint32_t w) { return (w >> 8) & 0xFFu; }
-__device__ inline uint32_t ws_prog(uint32_t w) { return w & 0xFFu; }
+static_assert(WD_TILE == SegWork::TILE, "the shared workspace's tile");
 // record word: position | EX << 8 | kind << 9 | row head << 16 | own-run head << 17
 constexpr uint32_t WK_NONE = 0, WK_OWN = 1, WK_WAITER = 2, WK_DYN = 3;
 constexpr uint32_t WI_EX = 1u << 8, WI_HEAD = 1u << 16, WI_OHEAD = 1u << 17;
@@ -112,123 +96,32 @@ __device__ inline uint32_t wi_kind(uint32_t info) { return (info >> 9) & 3u; }
 // flag byte of a dynamic access: conflict / die under the certain sets, under the possible sets
 constexpr uint32_t WF_CC = 1, WF_CD = 2, WF_PC = 4, WF_PD = 8;
 
-__device__ inline bool wd_state_ok(uint8_t rc) {
-  return rc == DCC_WD_RUN || rc == DCC_RC_RCOK || rc == DCC_RC_WAIT || rc == DCC_RC_ABORT || rc == DCC_WD_GONE;
-}
-
-// ---------------------------------------------------------------- check
-// The batch's and the state's validity before anything indexes with them and
-// before anything is written; the key bits and timestamp bits that vary; the
-// RUN txns (epoch, `leave` null: the ring word round 1 reads) or the leavers
-// that were not GONE (release).
-__global__ __launch_bounds__(WD_T) void k_wd_check(const uint32_t* __restrict__ off, uint64_t n,
-                                                   const uint64_t* __restrict__ keys, uint64_t nnz,
-                                                   const uint64_t* __restrict__ ts,
-                                                   const uint8_t* __restrict__ rc,
-                                                   const uint32_t* __restrict__ pos,
-                                                   const uint8_t* __restrict__ leave, uint32_t* __restrict__ cnt) {
-  __shared__ uint64_t s_a[WD_T / 64], s_b[WD_T / 64], s_e[WD_T / 64], s_f[WD_T / 64];
-  __shared__ uint32_t s_c[WD_T / 64], s_d[WD_T / 64];
-  uint32_t len = 0, err = 0, count = 0;
-  uint64_t kor = 0, knor = 0, tor = 0, tnor = 0;
-  const uint64_t tid = (uint64_t)blockIdx.x * WD_T + threadIdx.x, stride = (uint64_t)gridDim.x * WD_T;
-  for (uint64_t t = tid; t < n; t += stride) {
-    uint32_t l;
-    if (!check_span(off, t, n, nnz, err, len, l)) continue;
-    const uint8_t r = rc[t];
-    const uint32_t p = pos[t];
-    if (!wd_state_ok(r)) err |= WD_ERR_RC;
-    else if (r != DCC_WD_GONE && (p > l || (r == DCC_RC_RCOK && p != l) || (r == DCC_RC_WAIT && p >= l)))
-      err |= WD_ERR_POS;
-    const uint64_t v = ts[t];
-    tor |= v;
-    tnor |= ~v;
-    count += leave ? (leave[t] != 0 && r != DCC_WD_GONE) : (r == DCC_WD_RUN);
+// live_txn.h's engine type
+struct WdLive {
+  static constexpr uint32_t T = WD_T;
+  static constexpr const char* name = "waitdie";
+  static constexpr bool TS_RANGE = false, WAIT_STAYS = false, ROW_BIT = true, ABORT_POS = false;
+  // owned below pos, waited at at the pos of a WAIT txn, dynamic from the pos
+  // of a RUN txn on; the EX requests are the counted ones
+  __device__ static uint32_t record(uint8_t r, uint32_t p, uint32_t a, uint32_t ty, bool& dyn, bool& req) {
+    const uint32_t ex = is_ex(ty);
+    uint32_t kind = WK_NONE;
+    if (r != DCC_WD_GONE) {
+      if (a < p) kind = WK_OWN;
+      else if (r == DCC_RC_WAIT && a == p) kind = WK_WAITER;
+      else if (r == DCC_WD_RUN) kind = WK_DYN;
+    }
+    dyn = kind == WK_DYN;
+    req = dyn && ex;
+    return (ex ? WI_EX : 0u) | (kind << 9);
   }
-  for (uint64_t x = tid; x < nnz; x += stride) check_key(keys[x], err, kor, knor);
-  kor = block_reduce<WD_T / 64, OrOp<uint64_t>>(kor, s_a);
-  knor = block_reduce<WD_T / 64, OrOp<uint64_t>>(knor, s_b);
-  tor = block_reduce<WD_T / 64, OrOp<uint64_t>>(tor, s_e);
-  tnor = block_reduce<WD_T / 64, OrOp<uint64_t>>(tnor, s_f);
-  len = block_reduce<WD_T / 64, MaxOp<uint32_t>>(len, s_c);
-  err = block_reduce<WD_T / 64, OrOp<uint32_t>>(err, s_d);
-  if (threadIdx.x == 0) {
-    if (kor) atomicOr((unsigned long long*)&cnt[SEG_C_KOR], (unsigned long long)kor);
-    if (knor) atomicOr((unsigned long long*)&cnt[SEG_C_KNOR], (unsigned long long)knor);
-    if (tor) atomicOr((unsigned long long*)&cnt[WD_C_TOR], (unsigned long long)tor);
-    if (tnor) atomicOr((unsigned long long*)&cnt[WD_C_TNOR], (unsigned long long)tnor);
-    if (len) atomicMax(&cnt[SEG_C_MAXLEN], len);
-    if (err) atomicOr(&cnt[SEG_C_ERR], err);
+  // a possible conflict stops; on a certain one the txn dies if it dies for
+  // certain and waits if it cannot die
+  static constexpr uint32_t STOP = WF_PC, CERTAIN = WF_CC;
+  __device__ static uint32_t verdict(uint32_t f) {
+    return (f & WF_CC) && (f & WF_CD) ? LS_ABORT : ((f & WF_CC) && !(f & WF_PD) ? LS_WAIT : LS_UND);
   }
-  block_add<WD_T / 64>(count, leave ? &cnt[WD_C_LEFT] : &cnt[WD_C_RING + 1]);
-}
-
-struct WdArgs {
-  uint64_t n, m;
-  const uint32_t* off;
-  const uint64_t* keys;
-  const uint8_t* at;
-  const uint64_t* ts;
-  uint8_t* rc;       // the state, updated in place by the final pass
-  uint32_t* pos;
-  uint32_t lp;       // log2 lanes per txn
-  uint4* arec;       // [m] {txn, record word, ts lo, ts hi} of every access
-  uint32_t* stp;     // [n] state << 8 | progress
-  uint8_t* flg;      // [m] WF_* of every dynamic access, batch order
-  uint32_t* cnt;
 };
-
-// P lanes per txn (nowait_lanes.h).  Epoch: the sort key (packed row, dynamic)
-// and the record of every access; a RUN txn undecided at progress pos; the EX
-// requests and the RUN txns without one counted.
-__global__ __launch_bounds__(WD_T) void k_wd_prep(WdArgs A, KeyPack kp, uint64_t* __restrict__ ak,
-                                                  uint32_t* __restrict__ av) {
-  const Seg g = seg_of(A.lp);
-  const uint32_t gpb = WD_T >> A.lp;
-  uint32_t ro = 0, nex = 0;
-  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
-    const uint64_t t = g0 + g.gl;
-    const bool tv = t < A.n;
-    uint32_t o0 = 0, len = 0, p = 0;
-    uint8_t r = DCC_WD_GONE;
-    uint64_t tsv = 0;
-    if (tv) {
-      o0 = A.off[t];
-      len = A.off[t + 1] - o0;
-      tsv = A.ts[t];
-      r = A.rc[t];
-      p = A.pos[t];
-    }
-    const bool v = tv && g.a < len, run = r == DCC_WD_RUN;
-    const uint64_t x = (uint64_t)o0 + g.a;
-    bool exreq = false;
-    if (v) {
-      const uint32_t ex = is_ex(A.at[x] & 3u);
-      uint32_t kind = WK_NONE;
-      if (r != DCC_WD_GONE) {
-        if (g.a < p) kind = WK_OWN;
-        else if (r == DCC_RC_WAIT && g.a == p) kind = WK_WAITER;
-        else if (run) kind = WK_DYN;
-      }
-      exreq = kind == WK_DYN && ex;
-      ak[x] = (keypack_apply(kp, A.keys[x]) << 1) | (kind == WK_DYN ? 1ull : 0ull);
-      av[x] = (uint32_t)x;
-      A.arec[x] = make_uint4((uint32_t)t, g.a | (ex ? WI_EX : 0u) | (kind << 9), (uint32_t)tsv,
-                             (uint32_t)(tsv >> 32));
-    }
-    const uint64_t xb = ballot64(exreq) & g.mask;
-    if (tv && g.a == 0) {
-      A.stp[t] = run ? ws_word(WS_UND, WS_NOCAP, p) : ws_word(WS_STATIC, 0, 0);
-      if (run) {
-        ro += xb ? 0u : 1u;
-        nex += (uint32_t)__popcll(xb);
-      }
-    }
-  }
-  block_add<WD_T / 64>(ro, &A.cnt[WD_C_RO]);
-  __syncthreads();  // block_add's LDS words are read before the next call writes them
-  block_add<WD_T / 64>(nex, &A.cnt[WD_C_NEX]);
-}
 
 // The sorted records: sk / sv are the sorted keys and access indices.  A row
 // head is where the packed row changes; an own-run head is every access that
@@ -296,13 +189,13 @@ struct WdScan {
 
 // The element an access contributes under the current decisions.
 __device__ inline Wq wd_elem(uint32_t info, uint32_t st, uint64_t ts) {
-  const uint32_t q = info & 0xFFu, kind = wi_kind(info), state = ws_state(st), p = ws_prog(st), cap = ws_cap(st);
+  const uint32_t q = info & 0xFFu, kind = wi_kind(info), state = ls_state(st), p = ls_prog(st), cap = ls_cap(st);
   const bool dyn = kind == WK_DYN, ex = (info & WI_EX) != 0;
-  const bool cown = kind == WK_OWN || (dyn && (state == WS_OK || (state == WS_WAIT && q < p)));
-  const bool pown = cown || (dyn && state == WS_UND && q < cap);
-  const bool cwait = kind == WK_WAITER || (dyn && state == WS_WAIT && q == p);
-  const bool pwait = cwait || (dyn && state == WS_UND && q >= p && q <= cap);
-  const bool own = dyn && state == WS_UND && q < p;
+  const bool cown = kind == WK_OWN || (dyn && (state == LS_OK || (state == LS_WAIT && q < p)));
+  const bool pown = cown || (dyn && state == LS_UND && q < cap);
+  const bool cwait = kind == WK_WAITER || (dyn && state == LS_WAIT && q == p);
+  const bool pwait = cwait || (dyn && state == LS_UND && q >= p && q <= cap);
+  const bool own = dyn && state == LS_UND && q < p;
   Wq e;
   e.cmin = cown ? ts : ~0ull;
   e.pmin = pown ? ts : ~0ull;
@@ -331,7 +224,7 @@ __global__ __launch_bounds__(WD_T) void k_wd_scan(WdScan A) {
   for (uint32_t k = 0; k < WD_ITEMS; k++) {
     const bool v = base + k < A.m;
     info[k] = v ? A.s_info[base + k] : 0u;  // past the end: an identity element
-    st[k] = v ? A.stp[A.s_txn[base + k]] : ws_word(WS_STATIC, 0, 0);
+    st[k] = v ? A.stp[A.s_txn[base + k]] : ls_word(LS_STATIC, 0, 0);
     ts[k] = v ? A.s_ts[base + k] : 0;
   }
   Wq mine = WqOp::identity();
@@ -345,7 +238,7 @@ __global__ __launch_bounds__(WD_T) void k_wd_scan(WdScan A) {
   if (!APPLY) {
     bool und = false;
 #pragma unroll
-    for (uint32_t k = 0; k < WD_ITEMS; k++) und |= ws_state(st[k]) == WS_UND;
+    for (uint32_t k = 0; k < WD_ITEMS; k++) und |= ls_state(st[k]) == LS_UND;
     const bool any = __syncthreads_or(und);
     if (threadIdx.x == 0) {
       A.agg[blockIdx.x] = total;
@@ -357,7 +250,7 @@ __global__ __launch_bounds__(WD_T) void k_wd_scan(WdScan A) {
 #pragma unroll
   for (uint32_t k = 0; k < WD_ITEMS; k++) {
     const bool v = base + k < A.m;
-    if (v && wi_kind(info[k]) == WK_DYN && ws_state(st[k]) == WS_UND && (info[k] & 0xFFu) >= ws_prog(st[k])) {
+    if (v && wi_kind(info[k]) == WK_DYN && ls_state(st[k]) == LS_UND && (info[k] & 0xFFu) >= ls_prog(st[k])) {
       const Wq b = (info[k] & WI_HEAD) ? WqOp::identity() : run;
       const uint32_t ob = (info[k] & WI_OHEAD) ? 0u : b.bits;
       const bool ex = (info[k] & WI_EX) != 0;
@@ -372,90 +265,12 @@ __global__ __launch_bounds__(WD_T) void k_wd_scan(WdScan A) {
   }
 }
 
-// One round of decisions.  P lanes per txn, one access per lane: the first
-// access at or past the progress with a possible conflict is where the txn
-// dies, waits or stops.  Counts the txns it leaves undecided.
-__global__ __launch_bounds__(WD_T) void k_wd_advance(WdArgs A, const uint32_t* __restrict__ left,
-                                                     uint32_t* left_out) {
-  if (*left == 0) return;
-  const Seg g = seg_of(A.lp);
-  const uint32_t gpb = WD_T >> A.lp;
-  uint32_t und_left = 0;
-  for (uint64_t g0 = (uint64_t)blockIdx.x * gpb; g0 < A.n; g0 += (uint64_t)gridDim.x * gpb) {
-    const uint64_t t = g0 + g.gl;
-    const bool tv = t < A.n;
-    const uint32_t st = tv ? A.stp[t] : ws_word(WS_STATIC, 0, 0);
-    const bool und = tv && ws_state(st) == WS_UND;
-    if (!ballot64(und)) continue;  // the wave's txns are decided
-    uint32_t o0 = 0, len = 0;
-    if (und) {
-      o0 = A.off[t];
-      len = A.off[t + 1] - o0;
-    }
-    const bool v = und && g.a < len && g.a >= ws_prog(st);
-    const uint32_t f = v ? A.flg[(uint64_t)o0 + g.a] : 0u;
-    const uint64_t sb = ballot64((f & WF_PC) != 0) & g.mask;
-    const uint64_t ccb = ballot64((f & WF_CC) != 0), cdb = ballot64((f & WF_CD) != 0),
-                   pdb = ballot64((f & WF_PD) != 0);
-    if (und && g.a == 0) {
-      uint32_t w;
-      if (!sb) {
-        w = ws_word(WS_OK, 0, len);
-      } else {
-        const uint32_t l = (uint32_t)__builtin_ctzll(sb);
-        const bool cc = (ccb >> l) & 1ull, cd = (cdb >> l) & 1ull, pd = (pdb >> l) & 1ull;
-        const uint32_t s = cc && cd ? WS_DIE : (cc && !pd ? WS_WAIT : WS_UND);
-        const uint64_t cf = ccb & g.mask;  // certain conflicts at or past the progress: they stay certain
-        w = ws_word(s, cf ? (uint32_t)__builtin_ctzll(cf) - g.seg0 : WS_NOCAP, l - g.seg0);
-        und_left += s == WS_UND ? 1u : 0u;
-      }
-      A.stp[t] = w;
-    }
-  }
-  block_add<WD_T / 64>(und_left, left_out);
-}
-
-// The new state of the RUN txns: (RCOK, len), (WAIT, stop) or (ABORT, the
-// input pos); the conflict ordinals; the counts.
-__global__ __launch_bounds__(WD_T) void k_wd_final(uint64_t n, const uint32_t* __restrict__ stp,
-                                                   uint8_t* __restrict__ rc, uint32_t* __restrict__ pos,
-                                                   uint32_t* __restrict__ conflict, uint32_t* __restrict__ cnt) {
-  uint32_t ok = 0, die = 0, wait = 0, bad = 0;
-  for (uint64_t t = (uint64_t)blockIdx.x * WD_T + threadIdx.x; t < n; t += (uint64_t)gridDim.x * WD_T) {
-    const uint32_t st = stp[t], s = ws_state(st), p = ws_prog(st);
-    uint32_t c = DCC_ACCESS_NONE;
-    if (s == WS_OK) {
-      rc[t] = DCC_RC_RCOK;
-      pos[t] = p;
-      ok++;
-    } else if (s == WS_WAIT) {
-      rc[t] = DCC_RC_WAIT;
-      pos[t] = p;
-      c = p;
-      wait++;
-    } else if (s == WS_DIE) {
-      rc[t] = DCC_RC_ABORT;
-      c = p;
-      die++;
-    } else if (s == WS_UND) {
-      bad = 1;
-    }
-    if (conflict) conflict[t] = c;
-  }
-  if (bad) atomicOr(&cnt[SEG_C_ERR], WD_ERR_STATE);
-  block_add<WD_T / 64>(ok, &cnt[WD_C_OK]);
-  __syncthreads();
-  block_add<WD_T / 64>(die, &cnt[WD_C_DIE]);
-  __syncthreads();
-  block_add<WD_T / 64>(wait, &cnt[WD_C_WAIT]);
-}
-
 // -------------------------------------------------------------- release
 // P lanes per txn: the first sort's key of every access, the complement of
 // its txn's packed ts (descending ts; input order is txn index order, which
 // the stable sorts keep), and its record.  Only the accesses a staying txn
 // owns or waits at take part; the others become identity elements.
-__global__ __launch_bounds__(WD_T) void k_wd_rprep(WdArgs A, const uint8_t* __restrict__ leave, KeyPack tp,
+__global__ __launch_bounds__(WD_T) void k_wd_rprep(LiveArgs A, const uint8_t* __restrict__ leave, KeyPack tp,
                                                    uint64_t* __restrict__ ak, uint32_t* __restrict__ av) {
   const Seg g = seg_of(A.lp);
   const uint32_t gpb = WD_T >> A.lp;
@@ -568,101 +383,22 @@ __global__ __launch_bounds__(WD_T) void k_wd_rscan(WdRel A) {
     }
     run = RqOp::combine(run, e[k]);
   }
-  block_add<WD_T / 64>(prom, &A.cnt[WD_C_PROM]);
-}
-
-__global__ __launch_bounds__(WD_T) void k_wd_rgone(uint64_t n, const uint8_t* __restrict__ leave,
-                                                   uint8_t* __restrict__ rc) {
-  for (uint64_t t = (uint64_t)blockIdx.x * WD_T + threadIdx.x; t < n; t += (uint64_t)gridDim.x * WD_T)
-    if (leave[t]) rc[t] = DCC_WD_GONE;
-}
-
-// What the check left in the pinned mirror: the rejection, or the batch's
-// shape, the timestamp bits that vary and the RUN txns / leavers.
-struct WdChecked : BatchShape {
-  uint32_t count = 0;
-  uint64_t tvar = 0;
-};
-int wd_checked(dcc_ctx* ctx, const uint32_t* hc, uint64_t n, uint64_t m, bool release, WdChecked& c) {
-  const uint32_t err = hc[SEG_C_ERR];
-  CR(batch_checked(ctx, hc, m, true, c));
-  if (err & WD_ERR_RC) return ctx->fail(DCC_EINVAL, "waitdie: an rc byte is none of the five states");
-  if (err & WD_ERR_POS)
-    return ctx->fail(DCC_EINVAL, "waitdie: a pos does not fit its state (pos > len, RCOK below len, WAIT at len)");
-  uint64_t a, b;
-  memcpy(&a, hc + WD_C_TOR, 8);
-  memcpy(&b, hc + WD_C_TNOR, 8);
-  c.tvar = n ? (a & b) : 0;
-  c.count = release ? hc[WD_C_LEFT] : hc[WD_C_RING + 1];
-  return DCC_OK;
-}
-
-// What a lock epoch and a release share up to ev0: the call's arguments
-// checked, the batch and the state arrays on the device, the check, the key
-// pack and the lanes' geometry.  A.n == 0 behind a DCC_OK: the empty batch.
-struct WdOpen {
-  uint64_t per_block = 0, tiles = 0;
-  bool dev = false;
-  const uint8_t* leave_dev = nullptr;
-  unsigned max_grid = 1;
-  WdChecked c;
-  KeyPack kp{};
-  WdArgs A{};  // rc, pos, cnt: the state and the counters on the device
-};
-int wd_open(dcc_ctx* ctx, const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_io, uint32_t* pos_io, bool release,
-            const uint8_t* leave_in, uint64_t* out_left, uint64_t* out_promoted, WdOpen& O) {
-  hipStream_t stream = ctx->stream;
-  if (!ts_in || !rc_io || !pos_io) return ctx->fail(DCC_EINVAL, "waitdie: null ts / rc / pos");
-  if (release && !leave_in) return ctx->fail(DCC_EINVAL, "waitdie: null leave");
-  CR(ctx->check_batch(b, false));  // the offsets are checked on the device (k_wd_check)
-  if (ctx->comm_ranks() > 1) return ctx->fail(DCC_ENOTSUP, "waitdie: single-GPU engine");
-  O.dev = (b->flags & DCC_DEVICE_PTRS) != 0;
-  if (out_left) *out_left = 0;
-  if (out_promoted) *out_promoted = 0;
-  if (b->n_txn == 0) return DCC_OK;
-  DevBatch d;
-  CR(ctx->stage_batch(b, d));
-  const uint64_t n = d.n, m = d.nnz;
-  CR(ctx->waitdie_reserve(n, m, !O.dev));
-  const uint64_t* ts_dev;
-  uint8_t* rc_dev;
-  uint32_t* pos_dev;
-  CR(ctx->waitdie_stage(n, O.dev, ts_in, rc_io, pos_io, leave_in, ts_dev, rc_dev, pos_dev, O.leave_dev));
-  SegWork& W = ctx->seg;
-  uint32_t* cnt = (uint32_t*)W.misc.p;
-  O.max_grid = (unsigned)ctx->n_cu * 16;
-
-  // reject a malformed batch or state before anything indexes with it: rc,
-  // pos and the outputs are untouched by a rejected call
-  CK(hipMemsetAsync(cnt, 0, WD_C_WORDS * 4, stream));
-  k_wd_check<<<launch_grid(std::max(n, m), WD_T * 4, O.max_grid), WD_T, 0, stream>>>(
-      d.off, n, d.keys, m, ts_dev, rc_dev, pos_dev, O.leave_dev, cnt);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(ctx->hmisc, cnt, WD_C_WORDS * 4, hipMemcpyDeviceToHost, stream));
-  CK(hipStreamSynchronize(stream));
-  CR(wd_checked(ctx, (const uint32_t*)ctx->hmisc, n, m, release, O.c));
-  O.kp = make_keypack(O.c.varying);
-  if (O.kp.bits > 63) return ctx->fail(DCC_ENOTSUP, "waitdie: the keys vary in all 64 bits");
-  O.per_block = WD_T >> O.c.lp;
-  O.tiles = (m + WD_TILE - 1) / WD_TILE;
-  O.A = WdArgs{n,      m,  d.off, d.keys, d.acctype, ts_dev, rc_dev, pos_dev,
-               O.c.lp, (uint4*)W.arec.p, (uint32_t*)W.stp.p, (uint8_t*)ctx->wd_flg.p, cnt};
-  return DCC_OK;
+  block_add<WD_T / 64>(prom, &A.cnt[LV_C_PROM]);
 }
 
 }  // namespace
 
-int dcc_ctx::waitdie_reserve(uint64_t n, uint64_t nnz, bool host_arrays) {
+int dcc_ctx::live_reserve(uint64_t n, uint64_t nnz, bool host_arrays) {
   const uint64_t nn = std::max<uint64_t>(n, 1), mm = std::max<uint64_t>(nnz, 1);
   CR(seg.reserve(this, n, nnz));
-  CR(wd_flg.ensure(this, mm, "waitdie access flags"));
+  CR(lv_flg.ensure(this, mm, "waitdie access flags"));
   CR(cv_scratch.ensure(this, rs_scratch_words(mm) * 4 + 64, "radix scratch"));
   if (host_arrays) {
-    CR(wd_hts.ensure(this, nn * 8, "waitdie timestamps"));
-    CR(wd_hrc.ensure(this, nn, "waitdie rc"));
-    CR(wd_hpos.ensure(this, nn * 4, "waitdie pos"));
-    CR(wd_hleave.ensure(this, nn, "waitdie leave"));
-    CR(wd_conf.ensure(this, nn * 4, "waitdie conflicts"));
+    CR(lv_hts.ensure(this, nn * 8, "waitdie timestamps"));
+    CR(lv_hrc.ensure(this, nn, "waitdie rc"));
+    CR(lv_hpos.ensure(this, nn * 4, "waitdie pos"));
+    CR(lv_hleave.ensure(this, nn, "waitdie leave"));
+    CR(lv_conf.ensure(this, nn * 4, "waitdie conflicts"));
   }
   return DCC_OK;
 }
@@ -670,7 +406,7 @@ int dcc_ctx::waitdie_reserve(uint64_t n, uint64_t nnz, bool host_arrays) {
 // The arrays of a call on the device: a host call's are copied into the
 // context's staging buffers (and rc / pos copied back by the caller once the
 // call has succeeded).
-int dcc_ctx::waitdie_stage(uint64_t n, bool dev, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
+int dcc_ctx::live_stage(uint64_t n, bool dev, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
                            const uint8_t* leave, const uint64_t*& ts_d, uint8_t*& rc_d, uint32_t*& pos_d,
                            const uint8_t*& leave_d) {
   dcc_ctx* ctx = this;
@@ -679,24 +415,23 @@ int dcc_ctx::waitdie_stage(uint64_t n, bool dev, const uint64_t* ts, uint8_t* rc
   pos_d = pos;
   leave_d = leave;
   if (dev) return DCC_OK;
-  CK(hipMemcpyAsync(wd_hts.p, ts, n * 8, hipMemcpyHostToDevice, stream));
-  CK(hipMemcpyAsync(wd_hrc.p, rc, n, hipMemcpyHostToDevice, stream));
-  CK(hipMemcpyAsync(wd_hpos.p, pos, n * 4, hipMemcpyHostToDevice, stream));
-  if (leave) CK(hipMemcpyAsync(wd_hleave.p, leave, n, hipMemcpyHostToDevice, stream));
-  ts_d = (const uint64_t*)wd_hts.p;
-  rc_d = (uint8_t*)wd_hrc.p;
-  pos_d = (uint32_t*)wd_hpos.p;
-  leave_d = leave ? (const uint8_t*)wd_hleave.p : nullptr;
+  CK(hipMemcpyAsync(lv_hts.p, ts, n * 8, hipMemcpyHostToDevice, stream));
+  CK(hipMemcpyAsync(lv_hrc.p, rc, n, hipMemcpyHostToDevice, stream));
+  CK(hipMemcpyAsync(lv_hpos.p, pos, n * 4, hipMemcpyHostToDevice, stream));
+  if (leave) CK(hipMemcpyAsync(lv_hleave.p, leave, n, hipMemcpyHostToDevice, stream));
+  ts_d = (const uint64_t*)lv_hts.p;
+  rc_d = (uint8_t*)lv_hrc.p;
+  pos_d = (uint32_t*)lv_hpos.p;
+  leave_d = leave ? (const uint8_t*)lv_hleave.p : nullptr;
   return DCC_OK;
 }
 
 int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* rc_io, uint32_t* pos_io,
                            uint32_t* out_conflict, dcc_stats* st) {
   dcc_ctx* ctx = this;
-  EpochStats es;
-  dcc_stats& S = es.S;
-  WdOpen O;
-  CR(wd_open(this, b, ts_in, rc_io, pos_io, false, nullptr, nullptr, nullptr, O));
+  LiveOpen O;
+  dcc_stats& S = O.es.S;
+  CR(live_open<WdLive>(this, b, ts_in, rc_io, pos_io, false, nullptr, nullptr, nullptr, O));
   if (O.A.n == 0) {
     if (st) *st = S;
     return DCC_OK;
@@ -705,8 +440,8 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   const bool dev = O.dev, prof = profiling;
   const unsigned max_grid = O.max_grid;
   const KeyPack kp = O.kp;
-  const WdArgs& A = O.A;
-  uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)wd_conf.p) : nullptr;
+  const LiveArgs& A = O.A;
+  uint32_t* conf_dev = out_conflict ? (dev ? out_conflict : (uint32_t*)lv_conf.p) : nullptr;
   SegWork& W = seg;
   uint32_t* cnt = A.cnt;
 
@@ -715,7 +450,7 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
   uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
   const unsigned agrid = launch_grid(n, O.per_block, max_grid);
-  k_wd_prep<<<agrid, WD_T, 0, stream>>>(A, kp, kb[0], vb[0]);
+  k_live_prep<WdLive><<<agrid, WD_T, 0, stream>>>(A, kp, kb[0], vb[0]);
   CK(hipGetLastError());
   WdScan SA{};
   if (m) {
@@ -734,7 +469,7 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
   // which clears the ring word the round counts into / apply / advance.  The
   // lowest undecided txn is decided or moves its progress in every round.
   uint32_t rounds = 0;
-  CR(rounds_loop(this, cnt + WD_C_RING, n, n + m + 2, "waitdie", rounds,
+  CR(rounds_loop(this, cnt + LV_C_RING, n, n + m + 2, WdLive::name, rounds,
                  [&](uint32_t, const uint32_t* left, uint32_t* left_out, uint64_t) {
                    if (m) {
                      SA.left = left;
@@ -744,33 +479,31 @@ int dcc_ctx::waitdie_epoch(const dcc_batch* b, const uint64_t* ts_in, uint8_t* r
                    } else {
                      k_tile_aggscan<WqOp><<<1, SEG_AGG_T, 0, stream>>>(nullptr, nullptr, 0, left, left_out);
                    }
-                   k_wd_advance<<<agrid, WD_T, 0, stream>>>(A, left, left_out);
+                   k_live_advance<WdLive><<<agrid, WD_T, 0, stream>>>(A, left, left_out);
                  }));
 
   // rc / pos of a host call stay as they were unless the decisions are sound:
   // the final pass writes the staged copies
-  k_wd_final<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, A.stp, A.rc, A.pos, conf_dev, cnt);
+  k_live_final<WdLive><<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, A.stp, A.rc, A.pos, conf_dev, cnt);
   CK(hipGetLastError());
   if (prof) CK(hipEventRecord(pev[4], stream));
   CK(hipEventRecord(ev1, stream));
-  CK(hipMemcpyAsync(hmisc, cnt, WD_C_RING * 4, hipMemcpyDeviceToHost, stream));
+  CK(hipMemcpyAsync(hmisc, cnt, LV_C_RING * 4, hipMemcpyDeviceToHost, stream));
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
-  if (hc[SEG_C_ERR] & WD_ERR_STATE) return fail(DCC_EIO, "waitdie: inconsistent decisions");
+  if (hc[SEG_C_ERR] & LV_ERR_STATE) return fail(DCC_EIO, "waitdie: inconsistent decisions");
   S.rounds = rounds;
-  S.n_commit = hc[WD_C_OK];
-  S.n_abort = hc[WD_C_DIE];
-  S.n_survivors = hc[WD_C_WAIT];
-  S.nnz_w = hc[WD_C_NEX];
-  S.n_readonly = hc[WD_C_RO];
+  S.n_commit = hc[LV_C_OK];
+  S.n_abort = hc[LV_C_ABORT];
+  S.n_survivors = hc[LV_C_WAIT];
+  S.nnz_w = hc[LV_C_NREQ];
+  S.n_readonly = hc[LV_C_RO];
   if (!dev) {
-    CK(hipMemcpyAsync(rc_io, A.rc, n, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(pos_io, A.pos, n * 4, hipMemcpyDeviceToHost, stream));
-    if (out_conflict) CK(hipMemcpyAsync(out_conflict, conf_dev, n * 4, hipMemcpyDeviceToHost, stream));
+    CR(live_copy_back(this, O, rc_io, pos_io, out_conflict));
     CK(hipStreamSynchronize(stream));
   }
   S.alg_bytes = dcc_waitdie_alg_bytes(n, m, out_conflict != nullptr);
-  CR(es.finish(this, 4));
+  CR(O.es.finish(this, 4));
   if (st) *st = S;
   return DCC_OK;
 }
@@ -779,38 +512,35 @@ int dcc_ctx::waitdie_release(const dcc_batch* b, const uint64_t* ts_in, uint8_t*
                              const uint8_t* leave_in, uint64_t* out_left, uint64_t* out_promoted,
                              dcc_stats* st) {
   dcc_ctx* ctx = this;
-  EpochStats es;
-  dcc_stats& S = es.S;
-  WdOpen O;
-  CR(wd_open(this, b, ts_in, rc_io, pos_io, true, leave_in, out_left, out_promoted, O));
+  LiveOpen O;
+  dcc_stats& S = O.es.S;
+  CR(live_open<WdLive>(this, b, ts_in, rc_io, pos_io, true, leave_in, out_left, out_promoted, O));
   if (O.A.n == 0) {
     if (st) *st = S;
     return DCC_OK;
   }
   const uint64_t n = O.A.n, m = O.A.m, tiles = O.tiles;
   const unsigned max_grid = O.max_grid;
-  const KeyPack kp = O.kp, tp = make_keypack(O.c.tvar);
-  const WdArgs& A = O.A;
+  const KeyPack kp = O.kp, tp = make_keypack(O.tvar);
+  const LiveArgs& A = O.A;
   SegWork& W = seg;
 
   CK(hipEventRecord(ev0, stream));
   if (m) {
-    uint64_t* kb[2] = {(uint64_t*)W.k[0].p, (uint64_t*)W.k[1].p};
-    uint32_t* vb[2] = {(uint32_t*)W.v[0].p, (uint32_t*)W.v[1].p};
     const unsigned mgrid = launch_grid(m, WD_T, max_grid);
+    const uint64_t* sk;
+    const uint32_t* sv;
     // the records hold what the passes below need of rc / pos / leave: the
     // state is only written behind them (the checked offsets cover every
     // access, so k_wd_rprep writes every key and record)
-    k_wd_rprep<<<launch_grid(n, O.per_block, max_grid), WD_T, 0, stream>>>(A, O.leave_dev, tp, kb[0], vb[0]);
-    CK(hipGetLastError());
-    const int c1 = radix_sort_u64(kb, vb, m, tp.bits, (uint32_t*)cv_scratch.p, stream);
-    uint64_t* kb2[2] = {kb[c1], kb[c1 ^ 1]};
-    uint32_t* vb2[2] = {vb[c1], vb[c1 ^ 1]};
-    k_wd_rkey<<<mgrid, WD_T, 0, stream>>>(m, A.arec, A.keys, kp, vb2[0], kb2[0]);
-    CK(hipGetLastError());
-    const int c2 = radix_sort_u64(kb2, vb2, m, kp.bits + 1, (uint32_t*)cv_scratch.p, stream);
-    k_wd_rseg<<<mgrid, WD_T, 0, stream>>>(m, A.arec, kb2[c2], vb2[c2], (uint32_t*)W.stxn.p,
-                                          (uint32_t*)W.sinfo.p);
+    CR(live_sort_ts_row(
+        this, m, tp.bits, kp.bits + 1,
+        [&](uint64_t* ak, uint32_t* av) {
+          k_wd_rprep<<<launch_grid(n, O.per_block, max_grid), WD_T, 0, stream>>>(A, O.leave_dev, tp, ak, av);
+        },
+        [&](const uint32_t* v, uint64_t* k) { k_wd_rkey<<<mgrid, WD_T, 0, stream>>>(m, A.arec, A.keys, kp, v, k); },
+        sk, sv));
+    k_wd_rseg<<<mgrid, WD_T, 0, stream>>>(m, A.arec, sk, sv, (uint32_t*)W.stxn.p, (uint32_t*)W.sinfo.p);
     CK(hipGetLastError());
     const WdRel R{m,       (const uint32_t*)W.stxn.p, (const uint32_t*)W.sinfo.p, (uint64_t*)W.agg.p,
                   (uint64_t*)W.agg.p + tiles, A.rc,   A.pos,                       A.cnt};
@@ -819,21 +549,18 @@ int dcc_ctx::waitdie_release(const dcc_batch* b, const uint64_t* ts_in, uint8_t*
     k_wd_rscan<true><<<(unsigned)tiles, WD_T, 0, stream>>>(R);
     CK(hipGetLastError());
   }
-  k_wd_rgone<<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, O.leave_dev, A.rc);
+  k_live_gone<WdLive><<<launch_grid(n, WD_T, max_grid), WD_T, 0, stream>>>(n, O.leave_dev, A.rc, nullptr);
   CK(hipGetLastError());
   CK(hipEventRecord(ev1, stream));
-  CK(hipMemcpyAsync(hmisc, A.cnt, WD_C_RING * 4, hipMemcpyDeviceToHost, stream));
-  if (!O.dev) {
-    CK(hipMemcpyAsync(rc_io, A.rc, n, hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(pos_io, A.pos, n * 4, hipMemcpyDeviceToHost, stream));
-  }
+  CK(hipMemcpyAsync(hmisc, A.cnt, (LV_C_PROM + 1) * 4, hipMemcpyDeviceToHost, stream));
+  CR(live_copy_back(this, O, rc_io, pos_io));
   CK(hipStreamSynchronize(stream));
   const uint32_t* hc = (const uint32_t*)hmisc;
-  S.n_commit = O.c.count;
-  S.n_survivors = hc[WD_C_PROM];
+  S.n_commit = O.count;
+  S.n_survivors = hc[LV_C_PROM];
   if (out_left) *out_left = S.n_commit;
   if (out_promoted) *out_promoted = S.n_survivors;
-  CR(es.finish(this, 0));
+  CR(O.es.finish(this, 0));
   if (st) *st = S;
   return DCC_OK;
 }

@@ -5,9 +5,9 @@
 //
 // The stayers are a stream compaction over a ragged CSR: csr_select.h's tile
 // bodies with a Sel whose predicate is the state byte and whose rows are the
-// WAIT_DIE state.  New here: the state rule of k_wd_check applied in the
-// counting pass, a capacity verdict that covers stayers + fresh, and the
-// append, which starts at a base only the device knows.
+// WAIT_DIE state.  New here: the state rule of the epoch's check (live_txn.h)
+// applied in the counting pass, a capacity verdict that covers stayers +
+// fresh, and the append, which starts at a base only the device knows.
 //
 // Kernels:  k_wc_count    one pair per tile of SEL_T txns; the offsets and the
 //                         (rc, pos, revive) rule are checked here, the revived
@@ -35,6 +35,7 @@
 #include "dcc_ctx.h"
 #include "dcc_device.h"
 #include "dcc_scan.h"
+#include "live_txn.h"
 
 using namespace dcc;
 
@@ -48,8 +49,9 @@ constexpr uint32_t WC_ERR_RC = 4, WC_ERR_POS = 8, WC_ERR_REVIVE = 16, WC_ERR_FOF
 constexpr uint32_t WC_T = 256;  // threads per workgroup of the append
 
 // Txn t stays iff it is not GONE or is revived.  With CHECK (the counting
-// pass) take() also applies the state rule of k_wd_check (waitdie.hip), so an
-// accepted output is a state the epoch accepts, and counts the revived txns.
+// pass) take() also applies the state rule of the epoch's check (live_txn.h's
+// live_state_ok / live_pos_ok), so an accepted output is a state the epoch
+// accepts, and counts the revived txns.
 template <bool CHECK>
 struct CarrySel {
   const uint32_t* off;
@@ -71,14 +73,11 @@ struct CarrySel {
     const bool rev = revive && revive[t] != 0;
     if (CHECK) {
       uint32_t err = 0;
-      const bool known = r == DCC_WD_RUN || r == DCC_RC_RCOK || r == DCC_RC_WAIT || r == DCC_RC_ABORT ||
-                         r == DCC_WD_GONE;
-      if (!known) {
+      if (!live_state_ok(r)) {
         err = WC_ERR_RC;
       } else if (r != DCC_WD_GONE) {
-        const uint32_t p = pos[t], a0 = off[t], b0 = off[t + 1];
-        const uint32_t l = b0 - a0;
-        if (b0 >= a0 && (p > l || (r == DCC_RC_RCOK && p != l) || (r == DCC_RC_WAIT && p >= l))) err = WC_ERR_POS;
+        const uint32_t a0 = off[t], b0 = off[t + 1];
+        if (b0 >= a0 && !live_pos_ok(r, pos[t], b0 - a0)) err = WC_ERR_POS;
         if (rev) err |= WC_ERR_REVIVE;
       }
       if (err) atomicOr((unsigned long long*)&ctl[WC_C_ERR], (unsigned long long)err);
@@ -377,10 +376,10 @@ int dcc_ctx::waitdie_carry(const dcc_waitdie_carry_args* a, uint64_t* out_n, uin
   A.S.off = d.off;
   const bool w_src = out->src != nullptr;
   if (n) {
-    CR(stage(wd_hts, a->ts, n * 8, dev, "waitdie timestamps", A.S.ts));
-    CR(stage(wd_hrc, a->rc, n, dev, "waitdie rc", A.S.rc));
-    CR(stage(wd_hpos, a->pos, n * 4, dev, "waitdie pos", A.S.pos));
-    if (a->revive) CR(stage(wd_hleave, a->revive, n, dev, "waitdie revive", A.S.revive));
+    CR(stage(lv_hts, a->ts, n * 8, dev, "waitdie timestamps", A.S.ts));
+    CR(stage(lv_hrc, a->rc, n, dev, "waitdie rc", A.S.rc));
+    CR(stage(lv_hpos, a->pos, n * 4, dev, "waitdie pos", A.S.pos));
+    if (a->revive) CR(stage(lv_hleave, a->revive, n, dev, "waitdie revive", A.S.revive));
     if (a->src_in) CR(stage(sel_src, a->src_in, n * 4, dev, "select src", A.S.src_in));
   }
   WcFresh F{};
