@@ -317,6 +317,10 @@ _SIGS = [
     ("dcc_mvcc_finish", C.c_int,
      [_P, C.POINTER(Batch), _P, _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
     ("dcc_mvcc_access_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int, C.c_int]),
+    ("dcc_tso_access_epoch", C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, _P, C.POINTER(Stats)]),
+    ("dcc_tso_finish", C.c_int,
+     [_P, C.POINTER(Batch), _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(Stats)]),
+    ("dcc_tso_access_alg_bytes", C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int]),
     ("dcc_waitdie_carry", C.c_int,
      [_P, C.POINTER(WaitdieCarryArgs), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
       C.POINTER(Stats)]),

@@ -575,6 +575,14 @@ struct dcc_ctx {
                         uint32_t* out_conflict, dcc_stats* st);
   int mvcc_finish(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
                   uint64_t* vts, uint64_t* out_left, uint64_t* out_promoted, dcc_stats* st);
+  // TIMESTAMP with txns in flight (tso_live.hip).  The state is the caller's
+  // (rc, pos) arrays, the rows are the TIMESTAMP epoch's ts_rows above; the
+  // workspaces are the live-txn calls' and the TIMESTAMP epoch's head slots
+  int tso_live_reserve(uint64_t n, uint64_t nnz, bool host_arrays);
+  int tso_access_epoch(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, uint32_t* out_conflict,
+                       dcc_stats* st);
+  int tso_finish(const dcc_batch* b, const uint64_t* ts, uint8_t* rc, uint32_t* pos, const uint8_t* leave,
+                 uint64_t* out_left, uint64_t* out_promoted, dcc_stats* st);
 };
 
 // The host-side return-on-failure frame: CK takes a HIP call (the message goes

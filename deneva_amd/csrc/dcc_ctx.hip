@@ -297,6 +297,7 @@ extern "C" int dcc_reserve(dcc_ctx* ctx, uint64_t max_txn, uint64_t max_nnz) {
   if (!rc) rc = ctx->mvcc_reserve(max_txn, max_nnz, true, true);
   if (!rc) rc = ctx->live_reserve(max_txn, max_nnz, true);
   if (!rc) rc = ctx->mvcc_live_reserve(max_txn, max_nnz, true);
+  if (!rc) rc = ctx->tso_live_reserve(max_txn, max_nnz, true);
   if (!rc) rc = ctx->carry_reserve(max_txn, max_nnz);
   if (rc) return rc;
   return ctx->reserve_occ(max_txn, max_nnz, max_nnz, tw);

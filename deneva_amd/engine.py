@@ -860,6 +860,42 @@ class Engine:
                self._h)
         return int(left.value), int(prom.value), st.as_dict()
 
+    # ------------------------------------- TIMESTAMP with txns in flight
+    def tso_access_epoch(self, batch: EpochBatch, ts, rc, pos, want_conflict: bool = True):
+        """TIMESTAMP epoch with txns in flight (dcc_tso_access_epoch): the
+        WD_RUN txns send their requests from pos on against the pending
+        prewrites of the state and the context's TIMESTAMP rows (tso_rows_*).
+        rc and pos are updated in place.  Returns (rc[:n], pos[:n], conflict
+        u32[n] | None, stats); conflict[i] is the ordinal of the access a txn
+        waits or aborted at, ACCESS_NONE otherwise.  Arrays are numpy for a
+        host batch, device tensors for a device batch."""
+        n = batch.n_txn
+        keep, ptrs = self._waitdie_state("tso_access_epoch", batch, ts, rc, pos)
+        conf = None
+        if want_conflict:
+            if batch.on_device:
+                import torch
+                conf = torch.empty(max(n, 1), dtype=torch.int32, device=batch.offsets.device)
+            else:
+                conf = np.empty(max(n, 1), np.uint32)
+        st = _abi.Stats()
+        b = batch.to_c()
+        _check(lib.dcc_tso_access_epoch(self._h, C.byref(b), *ptrs, _ptr(conf), C.byref(st)), self._h)
+        return rc[:n], pos[:n], (conf[:n] if want_conflict else None), st.as_dict()
+
+    def tso_finish(self, batch: EpochBatch, ts, rc, pos, leave):
+        """dcc_tso_finish: the txns with leave[i] != 0 commit (RC_RCOK: wts =
+        max(wts, ts) per WR access) or abort (RC_ABORT, WD_RUN) and become
+        WD_GONE; buffered reads that no remaining prewrite blocks are promoted
+        to (WD_RUN, pos + 1) and raise rts.  rc and pos are updated in place.
+        Returns (n_left, n_promoted, stats)."""
+        keep, ptrs = self._waitdie_state("tso_finish", batch, ts, rc, pos, leave)
+        st = _abi.Stats()
+        b = batch.to_c()
+        left, prom = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.dcc_tso_finish(self._h, C.byref(b), *ptrs, C.byref(left), C.byref(prom), C.byref(st)), self._h)
+        return int(left.value), int(prom.value), st.as_dict()
+
     # ------------------------------------------- select by decision (carry)
     def select_batch(self, batch: EpochBatch, rc, want: int = _abi.RC_ABORT, src=None, out=None,
                      txn_base: int = 0, nnz_base: int = 0, want_src: bool = True):
@@ -1390,6 +1426,10 @@ def waitdie_carry_alg_bytes(n_txn: int, n_kept: int, nnz_kept: int, n_fresh: int
                             with_revive: bool = False, with_src: bool = True) -> int:
     return int(lib.dcc_waitdie_carry_alg_bytes(n_txn, n_kept, nnz_kept, n_fresh, nnz_fresh, int(with_revive),
                                                int(with_src)))
+
+
+def tso_access_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True) -> int:
+    return int(lib.dcc_tso_access_alg_bytes(n_txn, nnz, int(with_conflict)))
 
 
 def mvcc_access_alg_bytes(n_txn: int, nnz: int, with_conflict: bool = True, with_vts: bool = True) -> int:

@@ -557,7 +557,8 @@ uint64_t dcc_nowait_iso_alg_bytes(uint64_t n_txn, uint64_t nnz, uint64_t held_n,
  * that passes every access commits, and each of its WR accesses sends W_REQ:
  * wts = max(wts, ts) (row_ts.cpp:237-239).  In this model no request is ever
  * buffered or returns WAIT; Row_ts's buffered requests
- * (concurrent txns) and TS_TWR are out of scope.
+ * (concurrent txns) are dcc_tso_access_epoch / dcc_tso_finish below; TS_TWR
+ * is out of scope.
  *   ts              [n_txn] timestamps; NULL is DCC_EINVAL
  *   out_rc[i]       = DCC_RC_RCOK or DCC_RC_ABORT
  *   out_conflict[i] = for an aborted txn the ordinal within the txn (0-based
@@ -588,6 +589,89 @@ uint64_t dcc_tso_rows_size(const dcc_ctx* ctx);
  * + 9 nnz (key, type) + 24 nnz (one row: key, wts, rts, per access) + N (RC)
  * [+ 4N conflict]. */
 uint64_t dcc_tso_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
+
+/* -------------------------------------------- TIMESTAMP with txns in flight */
+/* Row_ts with its buffers (readreq, prereq, writereq and the cached min_rts /
+ * min_pts / min_wts; row_ts.cpp:64-165, :167-323) as two calls, the split of
+ * the in-flight MVCC calls below: an epoch that only sends requests -- it
+ * decides pass, wait or abort for every access and nothing finishes inside it
+ * -- and a finish the caller makes between epochs for the txns that are done,
+ * which raises wts, drops prewrites and promotes buffered reads as
+ * Row_ts::update_buffer does.  When other txns finish is thereby an input.
+ * DESIGN.md §8t has the arguments.
+ *
+ * State.  The WAIT_DIE / in-flight MVCC calls' (see there): caller-owned
+ * rc[n_txn] (u8, the same five bytes), pos[n_txn] (u32) and ts[n_txn] over a
+ * batch the caller keeps, so that dcc_waitdie_carry and dcc_batch_select move
+ * a TIMESTAMP population unchanged.  ts[i] is any u64, in any order, ties
+ * allowed, as for dcc_tso_validate_epoch; every comparison is the reference's
+ * unsigned `<` / `>`.  No value is reserved: a prewrite at UINT64_MAX behaves
+ * exactly as no prewrite, because min_pts is UINT64_MAX either way
+ * (row_ts.cpp:31, :157).  With len the txn's access count:
+ *   a txn that is not GONE holds one pending prewrite (ts[i]) on the row of
+ *   each of its WR accesses in [0, pos);
+ *   a WAIT txn (pos < len) has a buffered read on the row of access pos, and if
+ *   that access is a WR also that access's prewrite (P_REQ precedes R_REQ,
+ *   row.cpp:252-258);
+ *   a new txn is (RUN, 0); RCOK has pos == len.
+ * wts and rts of each row are the context's TIMESTAMP row table above, shared
+ * with dcc_tso_rows_set / get / clear / size and dcc_tso_validate_epoch.
+ * dcc_tso_validate_epoch ignores pending prewrites: calling it on a context
+ * while a population holds any is the caller's error.
+ *
+ * dcc_tso_access_epoch.  The RUN txns run in index order, each from pos[i], in
+ * list order (row_ts.cpp:167-208), against the state of all other txns, the
+ * prefixes the RUN txns hold and what the RUN txns before them did:
+ *   RD/SCAN   R_REQ: abort iff ts < wts (:176); else wait iff ts > the least
+ *             pending prewrite ts of the row (:178); else rts = max(rts, ts)
+ *             (:188-189);
+ *   WR        P_REQ: abort iff ts < rts or ts < wts (:193, :200; TS_TWR is
+ *             false); otherwise the prewrite becomes pending (:204) and R_REQ
+ *             follows.  The wait test is strict, so a txn's own prewrite and
+ *             ties never block it;
+ *   XP        sends nothing.
+ * First abort: (ABORT, ordinal); first wait: (WAIT, ordinal), out_conflict[i]
+ * the ordinal in both; past the last access (RCOK, len), DCC_ACCESS_NONE.  Txns
+ * that are not RUN are unchanged, their out_conflict is DCC_ACCESS_NONE.
+ * Cleanup is deferred: an aborted txn keeps the prewrites it made, old and new,
+ * until a finish releases it, and its rts bumps stay.  wts does not change
+ * inside an epoch.
+ *
+ * dcc_tso_finish.  leave[i] != 0 marks the txns that go.  An RCOK leaver
+ * commits: W_REQ per WR access, wts = max(wts, ts) (:236-244), and the prewrite
+ * goes.  An ABORT or RUN leaver aborts: XP_REQ per WR access in [0, pos)
+ * (:249-253).  A WAIT leaver is DCC_EINVAL (waits run from larger to smaller
+ * ts, so none lasts for ever); a GONE one is ignored.  The leavers become GONE.
+ * Then update_buffer (:268-323) per row: every buffered read with ts <= the
+ * least remaining pending prewrite ts executes: rts = max(rts, ts), and (WAIT,
+ * p) becomes (RUN, p + 1); there is no abort check at promotion, as in the
+ * reference.  A leaver's W_REQ is never buffered (writereq stays empty, so
+ * update_buffer's write branch, :300-320, is never reached),
+ * and applying all wts maxima and then promoting equals releasing the leavers
+ * one at a time, in any order.  *out_left (host, may be NULL) = the leavers
+ * that were not GONE, *out_promoted (host, may be NULL) = the promoted txns.
+ *
+ * Arrays (host or DCC_DEVICE_PTRS), compact batch forms, rejections (DCC_EINVAL
+ * with nothing written and the rows unchanged: malformed offsets, the reserved
+ * key, a txn longer than MAX_ROW_PER_TXN, NULL ts / rc / pos (leave for a
+ * finish), an rc byte outside the five states, pos > len, RCOK with pos != len,
+ * WAIT with pos >= len, a WAIT leaver), DCC_ENOTSUP for an epoch whose keys
+ * vary in all 64 bits, for a communicator of more than one rank and for
+ * DCC_ISO_* bits, rank 0 of a dcc_init_multi context and pipelined OCC epochs
+ * completing first are all exactly as the in-flight MVCC pair's.
+ * Stats of the epoch: n_commit / n_abort / n_survivors = the txns that became
+ * RCOK / ABORT / WAIT; nnz_w = WR requests (the WR accesses at or past pos of
+ * the RUN txns), n_readonly = RUN txns with none; rounds, device_ms, total_ms,
+ * alg_bytes; phase_ms as dcc_waitdie_lock_epoch.  Stats of the finish:
+ * n_commit = leavers, n_survivors = promoted, device_ms, total_ms. */
+int dcc_tso_access_epoch(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
+                         uint32_t* out_conflict /* may be NULL */, dcc_stats* out_stats);
+int dcc_tso_finish(dcc_ctx* ctx, const dcc_batch* batch, const uint64_t* ts, uint8_t* rc, uint32_t* pos,
+                   const uint8_t* leave, uint64_t* out_left, uint64_t* out_promoted /* host, may be NULL */,
+                   dcc_stats* out_stats);
+/* Algorithmic bytes of one access epoch: dcc_waitdie_alg_bytes (the 24-B row
+ * aggregate being rts, least pending prewrite, wts). */
+uint64_t dcc_tso_access_alg_bytes(uint64_t n_txn, uint64_t nnz, int with_conflict);
 
 /* ------------------------------------------------------------------ MVCC */
 /* Epoch under CC_ALG MVCC with one txn in flight at a time, the model of the
